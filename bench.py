@@ -20,6 +20,11 @@ member-parallel split) is the FULL record: one JSON line on stderr and
 
     python bench.py [--gpus N --steps K --warmup W]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline and nothing else: set up, settle the device clocks (SETTLE_STEPS untimed steps), W warm-ups,
+K timed steps, the line.  Everything described above beside the headline -- the end-to-end figures, the per-config scalars, the
+settled bracket, the completeness check, the back-to-back kernel time, the live PMC passes, `cpu_baseline` -- runs with `--full`.
+`--dump-outputs DIR` writes what the last timed step handed out (`DIR/mean.npy`, float32) in either form.
 """
 import argparse
 import faulthandler
@@ -85,7 +90,7 @@ LIVE_PMC_PASSES = (("fetch", ["FETCH_SIZE"]), ("write", ["WRITE_SIZE"]), ("sq", 
 
 def live_pmc(steps, warmup, timeout_s=75.0, kernel="k_score_cnn_mfma"):
     """`roofline.traffic` / `mfma_util_pmc` measured IN THIS RUN (round-5 verdict weak #8: they were replayed from a committed file):
-    three child runs of the headline step alone (`bench.py --no-extras --no-cpu-baseline --no-live-pmc`) under `rocprofv3 --pmc`, one
+    three child runs of the headline step alone (`bench.py --full --no-extras --no-cpu-baseline --no-live-pmc`) under `rocprofv3 --pmc`, one
     counter set per run as MI355X_MICROARCH.md prescribes (FETCH_SIZE and WRITE_SIZE do not fit one pass; no trace domains beside
     --pmc), per-dispatch means over the headline kernel's launches.  traffic = 2 x FETCH_SIZE (gfx950 tallies 128-byte requests at
     64 bytes) + WRITE_SIZE, KiB -> bytes; mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs).
@@ -107,7 +112,7 @@ def live_pmc(steps, warmup, timeout_s=75.0, kernel="k_score_cnn_mfma"):
         for label, counters in LIVE_PMC_PASSES:
             d = os.path.join(tmp, label)
             cmd = [exe, "--pmc", *counters, "-f", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                   "--steps", str(steps), "--warmup", str(warmup), "--no-extras", "--no-cpu-baseline", "--no-live-pmc", "--no-settled",
+                   "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-extras", "--no-cpu-baseline", "--no-live-pmc", "--no-settled",
                    "--full-record", os.path.join(tmp, f"full_{label}.json")]
             try:
                 pr = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, start_new_session=True)
@@ -403,6 +408,26 @@ def cpu_selftest(rank, world):
     return 0 if all(v["ok"] for v in out.values()) else 1
 
 
+SETTLE_STEPS = 3000              # ~0.55 s of headline steps: a cold device runs its first launches ~10 % slow (cold_start of the full record)
+
+
+def last_step_output(ens, steps):
+    """What the last of `steps` pipelined steps handed its caller: the `(n,)` ensemble mean, as a float32 host array.  `finish` only
+    waits for the slot's gather and hands out the slot's buffer, so asking again for the slot of step K - 1 returns that step's result
+    as long as no later launch has reused the slot."""
+    if steps < 1:
+        return None
+    return ens.finish((steps - 1) & 1).to("cpu").numpy().astype(np.float32)
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: DIR/<name>.npy for every array of the timed path's last step (the inputs and weights are seeded, so two
+    builds run with the same arguments can be compared output for output)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -413,6 +438,12 @@ def main():
     ap.add_argument("--mode", choices=("sequence", "member"), default="sequence",
                     help="headline split: sequence-parallel weak scaling of configs[1] (default) or member-parallel "
                          "strong scaling of an 8-member CNN ensemble")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the settled bracket, the completeness check of a step, "
+                         "per-config kernel times, end-to-end and explorer figures, the member-parallel split, the back-to-back kernel "
+                         "time, the live PMC passes and the CPU baseline (minutes; the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed out (the ensemble mean of the global batch) as DIR/mean.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline only (profiling passes)")
     ap.add_argument("--no-settled", action="store_true", help="skip the >= 0.5 s second bracket (profiling passes)")
@@ -438,6 +469,9 @@ def main():
                     help="run the launch path (self-spawn, rendezvous, launch/finish, one JSON line) on gloo with an "
                          "injected scorer; no GPU needed, not a measurement")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_live_pmc = args.no_settled = True
+        args.prepared = False
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher: become one.  N ranks, one per GPU, over RCCL; rank 0 prints the line.
@@ -505,7 +539,12 @@ def main():
         # sequence mode: the global batch (world x N rows); rank r reads rows [r N, (r+1) N) of it
         d_seq = torch.from_numpy(synth.random_sequence_bytes(glob_n, L, ALPHABET, seed=0)).cuda()
     ens.stream.synchronize()
+    if not args.full:
+        # a plain run has no other GPU work in front of its bracket (with --full the per-config blocks are, see below): the same
+        # untimed steps bring the clocks up, so that a short K reads the kernel and not the ramp
+        run_pipelined(ens, d_seq, glob_n, 0, SETTLE_STEPS, torch, dist, use_dist, 0)
     elapsed, host_issue_s, kern_ms = run_pipelined(ens, d_seq, glob_n, args.steps, args.warmup, torch, dist, use_dist, events_every(args.steps))
+    last_mean = last_step_output(ens, args.steps) if args.dump_outputs else None
     settled = None
     if elapsed < MIN_TIMED_S and not args.no_settled:
         # the driver's K steps are reported as asked; a K this short ends before the clocks settle, so a second,
@@ -516,19 +555,20 @@ def main():
 
     # ---- untimed completeness + correctness check of the last step
     got_mean = got_nm = None
-    for s_ in ens._slots:
-        if s_.planes is not None:
-            s_.planes.fill_(float("nan"))
-            s_.mean.fill_(float("nan"))
-    ens.launch(d_seq, glob_n, 0, "mean")
-    got_mean = ens.finish(0)
-    ens.launch(d_seq, glob_n, 1, "matrix")
-    got_nm = ens.finish(1)
-    torch.cuda.synchronize()
-    # scores are nan_to_num'ed, so a NaN that survives a step is an element nobody wrote
-    assert not bool(torch.isnan(got_mean).any()) and not bool(torch.isnan(got_nm).any()), "unwritten scores"
-    got_mean, got_nm = got_mean.cpu().numpy(), got_nm.cpu().numpy()
-    assert got_mean.shape == (glob_n,) and got_nm.shape == (glob_n, head_members)
+    if args.full:
+        for s_ in ens._slots:
+            if s_.planes is not None:
+                s_.planes.fill_(float("nan"))
+                s_.mean.fill_(float("nan"))
+        ens.launch(d_seq, glob_n, 0, "mean")
+        got_mean = ens.finish(0)
+        ens.launch(d_seq, glob_n, 1, "matrix")
+        got_nm = ens.finish(1)
+        torch.cuda.synchronize()
+        # scores are nan_to_num'ed, so a NaN that survives a step is an element nobody wrote
+        assert not bool(torch.isnan(got_mean).any()) and not bool(torch.isnan(got_nm).any()), "unwritten scores"
+        got_mean, got_nm = got_mean.cpu().numpy(), got_nm.cpu().numpy()
+        assert got_mean.shape == (glob_n,) and got_nm.shape == (glob_n, head_members)
 
     extras = {}
     if not args.no_extras:
@@ -537,7 +577,7 @@ def main():
         extras["member_parallel"] = bb.member_parallel_block(world, rank, local_rank, torch, dist, use_dist, args.steps, solo_group)
 
     if rank == 0:
-        assert np.array_equal(np.mean(got_nm, axis=1), got_mean), "device mean is not np.mean bit-for-bit"
+        assert not args.full or np.array_equal(np.mean(got_nm, axis=1), got_mean), "device mean is not np.mean bit-for-bit"
         cold = None
         confs = None
         if world == 1 and not args.no_extras:
@@ -550,6 +590,7 @@ def main():
             cold = {"ms_per_step": elapsed / args.steps * 1e3, "kernel_ms": kern_ms, "value": world * N * args.steps / elapsed,
                     "what": "the same W warm-ups + K timed steps as the first GPU work of the process (device clocks still ramping)"}
             elapsed, host_issue_s, kern_ms = run_pipelined(ens, d_seq, glob_n, args.steps, args.warmup, torch, dist, use_dist, events_every(args.steps))
+            last_mean = last_step_output(ens, args.steps) if args.dump_outputs else None
         out = make_report(world, N, args.steps, args.warmup, elapsed, host_issue_s, kern_ms, use_dist, args.mode,
                           head_members)
         if world == 1 and not args.no_live_pmc and not args.no_extras:
@@ -561,7 +602,7 @@ def main():
                 out["roofline"]["pmc_source"] = f"replayed (live passes failed): {out['roofline'].get('pmc_source')}"
         out["roofline"]["kernel_ms_events"] = (f"HIP event pairs on the launch stream around every {events_every(args.steps)}th K1 launch of the K timed steps "
                                                "(a pair around every launch cost the loop 7.8 us per step: profiles/r6_bench_loop_events.log)")
-        if world == 1 and args.mode == "sequence":
+        if world == 1 and args.mode == "sequence" and args.full:
             # the same launch back to back: ONE event pair around >= 40 ms of launches issued from C (no event latency inside the
             # bracket) -- the figure rocprofv3's per-dispatch mean agrees with
             try:
@@ -614,6 +655,8 @@ def main():
         if saved_stdout is not None:
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)
+        if args.dump_outputs and last_mean is not None:
+            dump_outputs(args.dump_outputs, {"mean": last_mean})
         full_path = write_full_record(out, args.full_record)
         _, text = contract_line(out, full_path)
         print(text, flush=True)

@@ -279,7 +279,7 @@ def test_bench_control_flow_with_two_ranks_on_one_gpu():
 
     full_path = os.path.join(tempfile.mkdtemp(), "bench_full.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--debug-share-device", "--steps", "6",
-                        "--warmup", "2", "--no-cpu-baseline", "--full-record", full_path], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--full-record", full_path], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) < 4096          # the contract line: the ONLY stdout line, short (round-5 verdict)
@@ -302,7 +302,7 @@ def test_bench_two_gpus_prints_one_line():
 
     full_path = os.path.join(tempfile.mkdtemp(), "bench_full.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--full-record", full_path], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--full-record", full_path], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) < 4096
@@ -311,3 +311,38 @@ def test_bench_two_gpus_prints_one_line():
     mp_ = {k: v for k, v in json.load(open(full_path))["member_parallel"].items() if k != "what"}
     assert all(v["checked"] for v in mp_.values())
     assert all(v["members_per_rank"] == 4 and v["speedup_vs_1gpu"] > 0 for v in mp_.values())
+
+
+def test_plain_bench_is_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the one line with the contract keys and none of the blocks that
+    `--full` adds; `--dump-outputs DIR` leaves DIR/mean.npy, float32: the ensemble mean the last timed step handed out, held here
+    against the float64 oracle on the same seeded batch and weights (tests/gpu_common.py's tolerance)."""
+    import json
+
+    from gpu_common import assert_scores
+    from flexs_amd import synth
+    from oracle import ref_np
+    from tools.bench_common import ALPHABET, F, H, K, L, M
+
+    n = 2000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", str(n),
+                        "--dump-outputs", str(tmp_path / "out"), "--full-record", str(tmp_path / "full.json")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "sequences/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3), rel=1e-4)
+    assert "cpu_baseline" not in d and "e2e_value" not in d and not any(k.startswith(("c1_", "settled_", "cold_")) for k in d["roofline"])
+    full = json.load(open(tmp_path / "full.json"))
+    assert not {"configs", "end_to_end", "member_parallel", "settled", "cold_start", "live_pmc", "cpu_baseline"} & set(full)
+    assert sorted(os.listdir(tmp_path / "out")) == ["mean.npy"]
+    got = np.load(tmp_path / "out" / "mean.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    seqs = synth.bytes_to_strings(synth.random_sequence_bytes(n, L, ALPHABET, seed=0))
+    shapes = ref_np.cnn_shapes(L, len(ALPHABET), F, H, K)
+    want = np.stack([ref_np.keras_fitness(seqs, ALPHABET, "cnn", synth.synthetic_weights(shapes, 1000 + m), exact=True)
+                     for m in range(M)], axis=1).mean(axis=1)
+    assert_scores(got, want, "bench --dump-outputs mean")

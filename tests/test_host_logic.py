@@ -225,10 +225,8 @@ def test_dyna_ppo_ensemble_gating():
 
 def test_tf_binding_host_tables_match_reference(golden_dir):
     """Host half of TFBinding (parse + normalise, tf_binding.py:31-41) against values captured from
-    the reference class; needs the reference's data file, so it only runs in the build container."""
-    path = "/root/reference/flexs/landscapes/data/tf_binding/SIX6_REF_R1_8mers.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference data files are not available on this machine")
+    the reference class, on the reference's SIX6_REF_R1 data file (tests/golden/, stored gzip-compressed: the parser reads it as is)."""
+    path = os.path.join(golden_dir, "SIX6_REF_R1_8mers.txt.gz")
     from flexs_amd.landscapes import TFBinding
 
     fx = json.load(open(os.path.join(golden_dir, "tf_binding.json")))
@@ -268,6 +266,32 @@ def test_bench_report_contract():
                           mode="member", members=8)
     assert m["scaling"] == "strong" and m["value"] == pytest.approx(100_000 * 10 / 0.01) and m["config"]["global_batch"] == 100_000
     assert m["roofline"]["flop_per_launch"] == 2.0 * 48628 * 1 * 100_000      # one member per rank
+
+
+def test_bench_dump_outputs_takes_the_last_steps_slot(tmp_path):
+    """`--dump-outputs`: the last of K double-buffered steps sits in slot (K - 1) & 1; what is written is a float32 copy of it."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class _Ens:
+        slots = [torch.tensor([1.0, 2.0]), torch.tensor([3.0, 4.0])]
+
+        def finish(self, slot):
+            return self.slots[slot]
+
+    assert bench.last_step_output(_Ens(), 0) is None
+    assert bench.last_step_output(_Ens(), 7).tolist() == [1.0, 2.0] and bench.last_step_output(_Ens(), 20).tolist() == [3.0, 4.0]
+    got = bench.last_step_output(_Ens(), 1)
+    _Ens.slots[0][0] = 9.0                                               # a copy: a later launch into the slot does not change it
+    assert got.dtype == np.float32 and got.tolist() == [1.0, 2.0]
+    bench.dump_outputs(str(tmp_path / "a" / "b"), {"mean": got})
+    back = np.load(tmp_path / "a" / "b" / "mean.npy")
+    assert back.dtype == np.float32 and np.array_equal(back, got)
 
 
 def test_issued_mfma_counts_follow_the_kernels_loop_bounds():
