@@ -650,6 +650,15 @@ class NativeModel:
         blob = np.concatenate([np.asarray(a, np.float32).ravel() for a in arrays])
         self.engine.check(self.engine._lib.fx_model_set_weights(self.handle, blob.ctypes.data_as(_f32p), blob.shape[0]))
 
+    def debug_conv1_table(self) -> np.ndarray:
+        """(1024, 32) conv1 outputs per window of five letters as the device built them (fx_debug_conv1_table; test hook)."""
+        out = np.empty((1024, 32), np.float32)
+        n = self.engine._lib.fx_debug_conv1_table(self.handle, out.ctypes.data_as(_f32p), out.size)
+        if n < 0:
+            _raise(int(n), self.engine.handle)
+        assert n == out.size
+        return out
+
     def get_blob(self) -> np.ndarray:
         blob = np.empty(self.num_params, np.float32)
         self.engine.check(self.engine._lib.fx_model_get_weights(self.handle, blob.ctypes.data_as(_f32p), blob.shape[0]))

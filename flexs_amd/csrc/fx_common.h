@@ -98,7 +98,14 @@ struct FxPackLayout {
     // the image (row (pi*16 + 4*c0 + c1) = row(2pi, c0) + row(2pi+1, c1)); -1 = none
     int64_t off_w1pair, pair_floats;   // MLP, 4 letters: pre-summed rows per pair of positions, FX_PAIR_PAD floats of padding per row
     int64_t alloc_floats;       // size of the packed buffer (total_floats + pair table)
+    // CNN on a 4-letter alphabet with seq_len 8, kernel size 5, two filter tiles and seven hidden tiles (the shapes of K1's C1T form): conv1's OUTPUT for every window of five letters, FX_C1T_WINDOWS rows of
+    // 32 floats (one 128-byte line) behind the packed buffer in d_packed: tab[w][16 mo + 4 g + r], w = sum_j code[s + j] * 4^j.  Built ON THE
+    // DEVICE from the packed conv1 rows and bias by fx_build_conv1_table (the kernel's own sequence of f32 adds and its integer-max ReLU, on the
+    // hardware that runs the gather: the same bits, NaN signs included); the host packer neither sees nor writes it.  -1 = none
+    int64_t off_c1tab, c1tab_floats;
+    int64_t dev_floats;         // size of d_packed (alloc_floats, rounded up to a line, + the conv1 table)
 };
+#define FX_C1T_WINDOWS 1024     // 4^5 windows
 
 FxPackLayout fx_pack_layout(const FxShape& s);
 // Position of hidden unit h inside the zero-padded 16*HT layout.  Hidden units are
@@ -180,6 +187,7 @@ struct fx_engine {
         int64_t zero_copy_calls = 0;   // host calls whose kernels read / wrote pinned host memory directly
         int64_t pair_evals = 0;        // (query, cache entry) distance evaluations
         int64_t train_steps = 0;       // mini-batch steps x members run by fx_train_fit
+        int64_t conv1_table_launches = 0;   // K1 launches that took the conv1-table form (read: option "conv1_table_launches")
     } counters;
     // deferred error word (device) + pinned host mirror
     unsigned* d_err = nullptr;
@@ -221,6 +229,7 @@ struct fx_engine {
     int64_t dense_few_waves_below = 0;    // auto: tiles per SIMD below which the 8-wave form is used (0 = never: measured no gain, profiles/archive/r2_dense_waves_ab.log)
     int64_t cnn_head_slab = 1;  // 4-letter CNN with more than 128 hidden units, batch launches (>= 16 tiles per workgroup): conv-only kernel + a head kernel that streams the H x H layer through LDS slabs
                                 // once per lockstep round of 8 tiles (k_cnn_head_slab) instead of the fused kernel, whose waves stream it from L2 per tile; 0 = the fused kernel (rounds 1-5)
+    int64_t cnn_conv1_table = 1; // K1, unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts: 1 = conv1's four outputs of a tile are READ from the member's table of all 4^5 windows (FxPackLayout::off_c1tab; eight 16-byte global loads per lane and tile) instead of gathered from LDS and summed; 0 = the gather (rounds 1-6: A/B).  Same bits
     int64_t cnn_quad_tail = 1;  // K1, unrolled seq_len = 8 form: the (tiles mod 4) last tiles of a workgroup are walked by wave quads in one round behind the main loop; 0 = one wave per tile throughout (rounds 1-5)
     int64_t wave_prio = 1;      // 1 = static, distinct issue priorities for the waves of a SIMD (fx_stagger_priority); 0 = A/B baseline
     int64_t trace = 0;          // 1 = the MFMA scoring kernels stamp an in-kernel timeline into d_trace (fx_debug_trace_read)
@@ -509,6 +518,9 @@ int fx_launch_score_generic(fx_engine* e, fx_model* const* models, int M, const 
 // returns FX_EUNSUPPORTED if no MFMA instantiation matches (caller falls back to generic)
 int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
                              int64_t N, float* d_out_NM, int Mtot, int m_off);
+// conv1's outputs for all 4^5 windows of a member whose layout has the table (FxPackLayout::off_c1tab), from the packed image already in
+// m->d_packed; a no-op for every other model.  fx_model_set_weights calls it: every path that changes weights goes through there
+int fx_build_conv1_table(fx_engine* e, fx_model* m);
 int fx_launch_cnn_pair_conv(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
                               int64_t N, float* d_out_NM, int Mtot, int m_off);

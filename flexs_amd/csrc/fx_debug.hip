@@ -108,6 +108,20 @@ int fx_debug_pack_weights(int kind, int L, int A, int F, int H, int K, const flo
     fx_pack_weights(s, blob, packed);
     return FX_OK;
 }
+// The conv1 table of a model as it lies in device memory (FxPackLayout::off_c1tab; FX_C1T_WINDOWS rows of 32 floats), for the tests that hold it
+// to the gather's arithmetic entry by entry.  Returns the number of floats copied; FX_EUNSUPPORTED: this shape has no table
+int64_t fx_debug_conv1_table(fx_model* m, float* out, int64_t cap) {
+    if (!m || !out) return FX_EINVAL;
+    fx_engine* e = m->eng;
+    const FxPackLayout& lay = m->layout;
+    if (lay.off_c1tab < 0) return FX_EUNSUPPORTED;
+    if (!m->has_weights) return fx_fail(e, FX_ESTATE, "model has no weights");
+    if (cap < lay.c1tab_floats) return FX_EINVAL;
+    FX_HIP(e, hipSetDevice(e->device));
+    FX_HIP(e, hipStreamSynchronize(e->stream));
+    FX_HIP(e, hipMemcpy(out, m->d_packed + lay.off_c1tab, sizeof(float) * (size_t)lay.c1tab_floats, hipMemcpyDeviceToHost));
+    return lay.c1tab_floats;
+}
 int fx_debug_mfma_probe(fx_engine* e, const float* a64, const float* b64, const float* c256, float* d256) {
     if (!e || !a64 || !b64 || !c256 || !d256) return FX_EINVAL;
     FX_HIP(e, hipSetDevice(e->device));

@@ -321,6 +321,7 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "ge_bytetab")) return &e->ge_bytetab;
     if (!std::strcmp(key, "wave_prio")) return &e->wave_prio;
     if (!std::strcmp(key, "cnn_quad_tail")) return &e->cnn_quad_tail;
+    if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
     if (!std::strcmp(key, "cnn_head_slab")) return &e->cnn_head_slab;
     if (!std::strcmp(key, "dense_pipe")) return &e->dense_pipe;
     if (!std::strcmp(key, "fuse_mean")) return &e->fuse_mean;
@@ -413,6 +414,7 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "lp_armed_served")) { *value = e->lp_armed_served; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_first_calls")) { *value = e->launch_first_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_first_redone")) { *value = e->launch_first_redone; return FX_OK; }
+    if (e && key && !std::strcmp(key, "conv1_table_launches")) { *value = e->counters.conv1_table_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "large_bar")) { *value = (e->large_bar && !e->rows_refused) ? 1 : 0; return FX_OK; }   // (the host can store into device memory: resident forms, launched-first calls)
     if (e && key && !std::strcmp(key, "server_streamed")) { *value = e->server.streamed; return FX_OK; }
@@ -468,7 +470,7 @@ int fx_model_create(fx_engine* e, int kind, int L, int A, int F, int H, int K, f
     m->blob.assign((size_t)np, 0.f);
     FX_HIP(e, hipSetDevice(e->device));
     if (hipMalloc(&m->d_blob, sizeof(float) * (size_t)np) != hipSuccess ||
-        hipMalloc(&m->d_packed, sizeof(float) * (size_t)m->layout.alloc_floats) != hipSuccess) {
+        hipMalloc(&m->d_packed, sizeof(float) * (size_t)m->layout.dev_floats) != hipSuccess) {
         (void)hipGetLastError();
         if (m->d_blob) (void)hipFree(m->d_blob);
         delete m;
@@ -520,6 +522,7 @@ int fx_model_set_weights(fx_model* m, const float* blob, int64_t n) {
     FX_HIP(e, hipStreamSynchronize(e->stream));
     FX_HIP(e, hipMemcpy(m->d_blob, m->blob.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     FX_HIP(e, hipMemcpy(m->d_packed, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    if (int rc = fx_build_conv1_table(e, m)) return rc;      // (on e->stream, in front of every launch that reads it)
     m->has_weights = true;
     m->bt_valid = false;
     return FX_OK;

@@ -87,6 +87,16 @@ FxPackLayout fx_pack_layout(const FxShape& s) {
         p.pair_floats = ((int64_t)(s.L / 2) * 16 + (s.L % 2) * 4) * (16 * p.HT + FX_PAIR_PAD);
     }
     p.alloc_floats = p.total_floats + p.pair_floats;
+    p.off_c1tab = -1;
+    p.c1tab_floats = 0;
+    p.dev_floats = p.alloc_floats;
+    // (only the shapes whose launches can take the table form -- score_cnn_mfma.hip: seq_len = 8, the canonical hidden width -- pay the 128 KiB
+    //  and the build kernel at every fx_model_set_weights)
+    if (s.kind == FX_CNN && s.A == 4 && s.K == 5 && s.L == 8 && p.FT == 2 && p.HT == 7) {
+        p.off_c1tab = rup(p.alloc_floats, 32);              // rows are whole 128-byte lines
+        p.c1tab_floats = (int64_t)FX_C1T_WINDOWS * 16 * p.FT;
+        p.dev_floats = p.off_c1tab + p.c1tab_floats;
+    }
     return p;
 }
 

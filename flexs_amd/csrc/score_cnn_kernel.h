@@ -48,6 +48,7 @@ struct CnnArgs {
     unsigned* seg_cnt;
     // packed-layout offsets (floats)
     int off_first, off_c2, off_c3, off_cb, off_w1p, conv_floats, off_d1, off_d2, off_db, total_floats;
+    int off_c1tab;              // C1T: the member's conv1 table behind its packed image (FxPackLayout::off_c1tab), never staged into LDS
     int stw_stride;             // STG: bytes of LDS scratch per wave (16 L rounded up to 16)
     int stw_ahead;              // STG: 1 = two scratches per wave, the next tile's bytes are asked for a tile ahead (fx_stage_tile_dma)
     FxRowsReady ready;          // launched-first host call: the rows arrive while the kernel runs (words == nullptr: they are all there)
@@ -111,9 +112,17 @@ __device__ __forceinline__ void fx_fused_mean_tile(float* planes, int64_t stride
 // Measured with it and NOT kept: a staged start (image by direct global -> LDS copies in two parts, every wave's first row asked for ahead of
 // the copies, first tiles start when the 35 KiB conv part has landed, the head part awaited through an LDS count) -- 1.5 % SLOWER on the
 // headline launch and on a one-member launch (profiles/r6_dma_start_ab.log; tools/archive/runs/r6_dma_start_ab.py).
+// C1T (the unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts): conv1's output at a position is a function
+// of five letters of a four-letter alphabet, so the member carries all 4^5 of them as a table behind its packed image (fx_build_conv1_table:
+// the gather's own adds and ReLU, the same bits).  A tile turns its row into codes through the LUT as before (same bad-character rule), cuts
+// four 10-bit window indices out of them and asks for its eight 16-byte pieces of the four table rows before the first conv2; there is no
+// conv1 gather (10 ds_read_b128, 20 packed adds, 32 integer maxima and the row addresses per position) and no code window.  The quad round
+// keeps the LDS gather.
 template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false>
+          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false>
 __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
+    static_assert(!C1T || (A == 4 && K == 5 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S == 4 && !SEG && HEAD && !STG),
+                  "C1T reads the table of 4^5 windows x 32 channels; the four positions of a seq_len = 8 row; built and measured in 16-wave workgroups");
     static_assert(!QT || (A == 4 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S > 0 && L1S <= 4 && !SEG && HEAD && !STG),
                   "QT is a form of the canonical unrolled kernel (exchange buffers of 8 KiB: four conv positions)");
     constexpr int QXT = 8;                                  // QT: 16-channel tiles per exchange buffer (>= FT * L1S, >= HT + 1)
@@ -189,6 +198,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
         const f4* w_c3 = reinterpret_cast<const f4*>(smem + p.off_c3);
         const float* cb = smem + p.off_cb;
         const float* w1p = smem + p.off_w1p;
+        [[maybe_unused]] const char* c1tab = C1T ? reinterpret_cast<const char*>(p.w[m] + p.off_c1tab) : nullptr;
         const float* dbase = DENSE_LDS ? smem : p.w[m];
         const f4* w_d1 = reinterpret_cast<const f4*>(dbase + p.off_d1);
         const f4* w_d2 = reinterpret_cast<const f4*>(dbase + p.off_d2);
@@ -272,6 +282,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
             // (any alignment: gfx950 compute runs with unaligned access enabled) and the positions are shifts, instead of eight byte loads:
             // -1 % on the headline launch
             constexpr bool ROW8 = !STG && L1S == 4 && K == 5;
+            static_assert(!C1T || ROW8, "C1T cuts its window indices out of the 8-byte row");
             [[maybe_unused]] unsigned long long rowq[NT];
             if constexpr (ROW8) {
 #pragma unroll
@@ -288,7 +299,24 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
             constexpr bool RING = (L1S > 0) || (K * K3 <= 16);
             constexpr int UN = L1S > 0 ? (L1S + PR2 + PR3) : (RING ? K * K3 : 1);   // trips per unrolled block
             // code window: alphabet index at positions s .. s+K-1
-            int cw[K][NT];
+            [[maybe_unused]] int cw[K][NT];
+            [[maybe_unused]] f4 c1t[C1T ? L1S : 1][FT];  // C1T: conv1's outputs of the tile's positions, on their way from the table
+            if constexpr (C1T) {
+                unsigned codes = 0;                       // two bits per letter of the row
+#pragma unroll
+                for (int j = 0; j < L1S + K - 1; ++j) {
+                    unsigned c = lut_s[seq_byte(0, j)];
+                    if (c == 0xFF) { bad = true; c = 0; }
+                    codes |= c << (2 * j);
+                }
+#pragma unroll
+                for (int s = 0; s < L1S; ++s) {
+                    // window s = letters s .. s + 4, letter j weighs 4^j; the mask keeps the row inside the table whatever the LUT holds
+                    const unsigned at = (((codes >> (2 * s)) & (unsigned)(FX_C1T_WINDOWS - 1)) << 7) | ((unsigned)g << 4);
+#pragma unroll
+                    for (int mo = 0; mo < FT; ++mo) c1t[s][mo] = *reinterpret_cast<const f4*>(c1tab + at + 64 * mo);
+                }
+            } else {
 #pragma unroll
             for (int j = 0; j < K - 1; ++j)
 #pragma unroll
@@ -297,6 +325,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
                     if (c == 0xFF) { bad = true; c = 0; }
                     cw[RING ? j : j + 1][nt] = c;         // (shifting form: moved down at the top of step 0)
                 }
+            }
             // Look-ahead queue of raw sequence bytes (generic-length form): the byte a step consumes was requested PF
             // steps earlier, so its L2 / HBM latency is off the step's critical path.  A lone wave (small batches:
             // one tile per SIMD) otherwise pays one global round trip per position (profiles/archive/r2_trace_probe: 8.4 us
@@ -390,7 +419,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
 #define FX_W2(j) (RING ? (u + K3 * K - PR2 + 1 + (j)) % K3 : (j))
 
                 // ---- conv1 (valid) at t1 = s
-                if (s < L1) {
+                if (!C1T && s < L1) {
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         int raw;
@@ -410,7 +439,11 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
                         cw[FX_CW(K - 1)][nt] = c;
                     }
                 }
-                if (s < L1 && act) {
+                if (C1T && s < L1) {
+                    // (L1S > 0: s == u)
+#pragma unroll
+                    for (int t = 0; t < FT; ++t) win1[FX_W1NEW][t][0] = c1t[C1T && u < L1S ? u : 0][t];
+                } else if (s < L1 && act) {
                     f4 o1[FT][NT];
                     init_bias<FT, NT>(cb, o1, g);
                     if (G1) {
@@ -639,10 +672,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
 }
 
 template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false>
+          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false>
 int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     constexpr int waves = WAVES;
-    auto kern = k_score_cnn_mfma<A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT>;
+    auto kern = k_score_cnn_mfma<A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT, C1T>;
     if (QT) lds_bytes += (size_t)3 * 2 * 8 * 1024;               // three quads' exchange buffers (2 x 8 KiB each)
     if (SEG) lds_bytes += (size_t)WAVES * FT * 64 * 16;          // segment-maxima slots
     const bool ahead = STG && e->cnn_stage_host >= 2 && lds_bytes + 2 * (size_t)WAVES * ((16 * (size_t)a_in.L + 15) / 16 * 16) <= (size_t)e->max_lds;
@@ -675,6 +708,7 @@ int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     if (SEG && HEAD && a.seg_sb > 1) blocks = U * a.seg_sb;       // multi-workgroup segment form: exactly units x seg_sb
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), lds_bytes, e->stream, a);
     FX_HIP(e, hipGetLastError());
+    if (C1T) e->counters.conv1_table_launches += 1;
 #if defined(FX_AB)
     if (a.fm_mean) e->fused_mean_done = true;
 #endif

@@ -58,9 +58,16 @@ int dispatch_a4(fx_engine* e, const CnnArgs& a0, int variant, bool big, size_t f
                 case 7:                                  // unrolled L = 8 specialisation with s_setprio (the default)
                     if (a.L != 8) return fx_fail(e, FX_EINVAL, "cnn_variant 7 is a seq_len = 8 specialisation");
                     // ... with the (tiles mod 4) last tiles of a workgroup walked by wave quads (round 6; cnn_quad_tail = 0: A/B)
-                    if (e->cnn_quad_tail && !e->rows_req.on && lds + (size_t)3 * 2 * 8 * 1024 <= (size_t)e->max_lds) {
-                        a.quad_tail = 1;
-                        return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true>(e, a, lds);
+                    // ... and conv1 read from the member's table of windows instead of gathered (cnn_conv1_table = 0: A/B); not when the
+                    // rows arrive while the kernel runs (the table's second round trip would stand behind the wait for the rows)
+                    {
+                        const bool c1t = e->cnn_conv1_table && !e->rows_req.on && a.off_c1tab >= 0;
+                        if (e->cnn_quad_tail && !e->rows_req.on && lds + (size_t)3 * 2 * 8 * 1024 <= (size_t)e->max_lds) {
+                            a.quad_tail = 1;
+                            if (c1t) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true, true>(e, a, lds);
+                            return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true>(e, a, lds);
+                        }
+                        if (c1t) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, false, true>(e, a, lds);
                     }
                     return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true>(e, a, lds);
                 case 11:                                 // unrolled L = 8 form in 8-wave workgroups (256-register budget): small launches
@@ -118,7 +125,32 @@ int dispatch_a4(fx_engine* e, const CnnArgs& a0, int variant, bool big, size_t f
     return dl ? launch_inst<4, 5, 2, HT_, 1, true, 8>(e, a, lds) : launch_inst<4, 5, 2, HT_, 1, false, 8>(e, a, lds);
 }
 
+// The conv1 table of one member (C1T): one thread per (window, four channels).  The arithmetic is the gather's, step for step -- the bias, then
+// the kernel rows of taps 0 .. 4 added in that order as f4 sums, then relu4 on the float bits -- and it runs on the device that runs the
+// gather, so infinities, NaNs (whose SIGN decides what the integer-max ReLU makes of them) and denormals come out as they do there.
+__global__ void __launch_bounds__(256) k_build_conv1_table(const float* packed, int off_cb, int off_w1p, float* tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;       // FX_C1T_WINDOWS x 8 threads
+    const int w = i >> 3, q = i & 7;                    // channels 4q .. 4q + 3 = 16 mo + 4 g + r
+    if (w >= FX_C1T_WINDOWS) return;
+    f4 o = *reinterpret_cast<const f4*>(packed + off_cb + 4 * q);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int c = (w >> (2 * j)) & 3;
+        o += *reinterpret_cast<const f4*>(packed + off_w1p + (j * 4 + c) * FX_C1_ROW(2) + 4 * q);
+    }
+    *reinterpret_cast<f4*>(tab + w * 32 + 4 * q) = relu4(o);
+}
+
 }  // namespace
+
+int fx_build_conv1_table(fx_engine* e, fx_model* m) {
+    const FxPackLayout& lay = m->layout;
+    if (lay.off_c1tab < 0) return FX_OK;
+    hipLaunchKernelGGL(k_build_conv1_table, dim3(FX_C1T_WINDOWS * 8 / 256), dim3(256), 0, e->stream, m->d_packed, (int)lay.off_cb,
+                       (int)lay.off_w1p, m->d_packed + lay.off_c1tab);
+    FX_HIP(e, hipGetLastError());
+    return FX_OK;
+}
 
 int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
                              int64_t N, float* d_out_NM, int Mtot, int m_off) {
@@ -153,6 +185,7 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
     a.off_first = (int)lay.off_first; a.off_c2 = (int)lay.off_c2; a.off_c3 = (int)lay.off_c3;
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
     a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
+    a.off_c1tab = (int)lay.off_c1tab;
 
 #if defined(FX_AB)
     // mean-only call with the rows resident in device memory and every member in this launch: the last member to finish a tile averages

@@ -459,6 +459,10 @@ int fx_train_orders(uint64_t seed, int64_t n, int epochs, int32_t *out);
  * fragment order) and the bit-parallel Levenshtein that the device kernels use,
  * so the CPU test-suite can check them against the oracle. */
 int64_t fx_debug_packed_size(int kind, int L, int A, int F, int H, int K);
+/* Needs the GPU: the conv1 table of a 4-letter seq_len = 8 CNN (conv1's output for every window of five letters, 1024 rows of 32
+ * floats, row w = sum_j code[j] * 4^j, channel order as packed) as the device built it at fx_model_set_weights.  Returns the
+ * number of floats copied (cap must hold 32768), FX_EUNSUPPORTED for shapes without a table. */
+int64_t fx_debug_conv1_table(fx_model *m, float *out, int64_t cap);
 int fx_debug_pack_layout(int kind, int L, int A, int F, int H, int K, int64_t *out16);
 /* v_mfma_f32_16x16x4_f32 instructions (2048 FLOP each) the MFMA scoring kernels issue per 16-sequence tile per
  * member for this shape -- the kernels' loop bounds restated on the host ('same'-padding taps and the one-hot
