@@ -659,6 +659,16 @@ class NativeModel:
         assert n == out.size
         return out
 
+    def debug_conv2_prefix(self, depth: int) -> np.ndarray:
+        """(3, 4 ** (4 + depth), 32) conv2 accumulators (pre-ReLU) after the first `depth` valid taps, per first-tap family j0 = 0, 1, 2 and index of
+        4 + depth letters, as the device built them (fx_debug_conv2_prefix; test hook)."""
+        out = np.empty((3, 4 ** (4 + depth), 32), np.float32)
+        n = self.engine._lib.fx_debug_conv2_prefix(self.handle, depth, out.ctypes.data_as(_f32p), out.size)
+        if n < 0:
+            _raise(int(n), self.engine.handle)
+        assert n == out.size
+        return out
+
     def get_blob(self) -> np.ndarray:
         blob = np.empty(self.num_params, np.float32)
         self.engine.check(self.engine._lib.fx_model_get_weights(self.handle, blob.ctypes.data_as(_f32p), blob.shape[0]))
@@ -816,6 +826,24 @@ def debug_pack_layout(kind, L, A, F, H, K) -> dict:
     names = ["FT", "HT", "SG1", "off_first", "off_c2", "off_c3", "off_cb", "conv_floats", "off_d1", "off_d2",
              "off_d3", "off_db", "RLH", "total_floats", "off_w1p", "HTR"]
     return dict(zip(names, list(v)))
+
+
+def debug_table_layout(kind, L, A, F, H, K) -> dict:
+    """Where the device-built tables lie behind the packed image (floats; -1 / 0: the shape has none)."""
+    v = (C.c_int64 * 8)()
+    rc = lib().fx_debug_table_layout(kind, L, A, F, H, K, v)
+    if rc != FX_OK:
+        raise ValueError(status_name(rc))
+    names = ["alloc_floats", "dev_floats", "off_c1tab", "c1tab_floats", "off_c2p1", "c2p1_floats", "off_c2p2", "c2p2_floats"]
+    return dict(zip(names, list(v)))
+
+
+def debug_conv2_prefix_row(codes: int, p: int, depth: int) -> int:
+    """Row (of 32 floats) of the depth's prefix tables that conv position p of a seq_len = 8 row reads; codes = two bits per letter."""
+    r = lib().fx_debug_conv2_prefix_row(codes, p, depth)
+    if r < 0:
+        raise ValueError(status_name(int(r)))
+    return int(r)
 
 
 def mfma_per_tile(kind, L, A, F, H, K) -> int:

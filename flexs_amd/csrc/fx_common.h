@@ -103,9 +103,30 @@ struct FxPackLayout {
     // DEVICE from the packed conv1 rows and bias by fx_build_conv1_table (the kernel's own sequence of f32 adds and its integer-max ReLU, on the
     // hardware that runs the gather: the same bits, NaN signs included); the host packer neither sees nor writes it.  -1 = none
     int64_t off_c1tab, c1tab_floats;
-    int64_t dev_floats;         // size of d_packed (alloc_floats, rounded up to a line, + the conv1 table)
+    // The same shapes, behind the conv1 table (K1's C2P form): conv2's ACCUMULATOR after its first `depth` valid taps, pre-ReLU, for depth d = 1 ..
+    // FX_C2P_MAX_DEPTH at off_c2p[d - 1]: three families j0 = 0, 1, 2 (the first valid tap of a position, fx_c2p_first_tap) of 4^(4 + d) rows of 32
+    // floats, T[j0][idx][16 mo + 4 g + r], idx = sum_i code[s + i] * 4^i over the 4 + d letters that the first d windows cover.  Built on the device
+    // from the conv1 table and the packed conv2 blocks by fx_build_conv2_prefix (the scoring kernel's own init_bias + mma_layer chain: the same bits).
+    // Every depth that is compiled in is allocated and built, so a member serves any value of the option cnn_conv2_prefix.  -1 = none
+    int64_t off_c2p[2], c2p_floats[2];
+    int64_t dev_floats;         // size of d_packed (alloc_floats, rounded up to a line, + the conv1 table + the conv2 prefix tables)
 };
 #define FX_C1T_WINDOWS 1024     // 4^5 windows
+#define FX_C2P_MAX_DEPTH 2      // conv2 prefix tables: depths compiled in (FxPackLayout::off_c2p has this many entries)
+#ifndef FX_C2P_DEFAULT
+#define FX_C2P_DEFAULT 2        // engine option cnn_conv2_prefix as shipped: the depth with the best bench.py median (profiles/conv2_prefix_ab.log; -DFX_C2P_DEFAULT=0 / 1 on fx_engine.hip: the A/B arms of bench.py)
+#endif
+#define FX_C2P_FAMILIES 3       // first valid taps j0 = 0, 1, 2 of the four conv positions of a seq_len = 8 row
+#define FX_C2P_ENTRIES(depth) (1 << (2 * (4 + (depth))))   // 4^5 rows per family at depth 1, 4^6 at depth 2
+// conv2 ('same', five taps, tap j reads out1[p + j - 2]) at position p of the four conv positions: its first valid tap, the window that tap reads
+// (= the first letter of the prefix index), and the index of the position's row in its depth's tables (rows of 32 floats; codes = two bits per
+// letter of the row, letter i at bits 2i).  The mask keeps the row inside the table whatever the codes hold.
+__host__ __device__ constexpr int fx_c2p_first_tap(int p) { return p < 2 ? 2 - p : 0; }
+__host__ __device__ constexpr int fx_c2p_first_window(int p) { return p > 2 ? p - 2 : 0; }
+__host__ __device__ constexpr unsigned fx_c2p_row(unsigned codes, int p, int depth) {
+    return (unsigned)fx_c2p_first_tap(p) * (unsigned)FX_C2P_ENTRIES(depth) +
+           ((codes >> (2 * fx_c2p_first_window(p))) & (unsigned)(FX_C2P_ENTRIES(depth) - 1));
+}
 
 FxPackLayout fx_pack_layout(const FxShape& s);
 // Position of hidden unit h inside the zero-padded 16*HT layout.  Hidden units are
@@ -188,6 +209,7 @@ struct fx_engine {
         int64_t pair_evals = 0;        // (query, cache entry) distance evaluations
         int64_t train_steps = 0;       // mini-batch steps x members run by fx_train_fit
         int64_t conv1_table_launches = 0;   // K1 launches that took the conv1-table form (read: option "conv1_table_launches")
+        int64_t conv2_prefix_launches = 0;  // ... and, of those, the ones that read conv2's first taps from the prefix tables (read: option "conv2_prefix_launches")
     } counters;
     // deferred error word (device) + pinned host mirror
     unsigned* d_err = nullptr;
@@ -230,6 +252,7 @@ struct fx_engine {
     int64_t cnn_head_slab = 1;  // 4-letter CNN with more than 128 hidden units, batch launches (>= 16 tiles per workgroup): conv-only kernel + a head kernel that streams the H x H layer through LDS slabs
                                 // once per lockstep round of 8 tiles (k_cnn_head_slab) instead of the fused kernel, whose waves stream it from L2 per tile; 0 = the fused kernel (rounds 1-5)
     int64_t cnn_conv1_table = 1; // K1, unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts: 1 = conv1's four outputs of a tile are READ from the member's table of all 4^5 windows (FxPackLayout::off_c1tab; eight 16-byte global loads per lane and tile) instead of gathered from LDS and summed; 0 = the gather (rounds 1-6: A/B).  Same bits
+    int64_t cnn_conv2_prefix = FX_C2P_DEFAULT; // K1, the conv1-table form (cnn_conv1_table = 1, rows resident, a member with tables): 1 / 2 = a tile READS conv2's accumulator after the first one / two valid taps of each of its four positions from the member's prefix tables (FxPackLayout::off_c2p; 64 / 128 fewer MFMAs per tile, 14 / 12 16-byte global loads per lane and tile instead of 8) and runs only the remaining taps; 0 = all taps.  Launches that cannot take the conv1-table form silently run without it.  Same bits
     int64_t cnn_quad_tail = 1;  // K1, unrolled seq_len = 8 form: the (tiles mod 4) last tiles of a workgroup are walked by wave quads in one round behind the main loop; 0 = one wave per tile throughout (rounds 1-5)
     int64_t wave_prio = 1;      // 1 = static, distinct issue priorities for the waves of a SIMD (fx_stagger_priority); 0 = A/B baseline
     int64_t trace = 0;          // 1 = the MFMA scoring kernels stamp an in-kernel timeline into d_trace (fx_debug_trace_read)
@@ -521,6 +544,9 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
 // conv1's outputs for all 4^5 windows of a member whose layout has the table (FxPackLayout::off_c1tab), from the packed image already in
 // m->d_packed; a no-op for every other model.  fx_model_set_weights calls it: every path that changes weights goes through there
 int fx_build_conv1_table(fx_engine* e, fx_model* m);
+// conv2's prefix tables of such a member (FxPackLayout::off_c2p, every depth compiled in) from the conv1 table and the packed conv2 blocks in
+// m->d_packed: enqueued on e->stream right behind fx_build_conv1_table; a no-op for every other model
+int fx_build_conv2_prefix(fx_engine* e, fx_model* m);
 int fx_launch_cnn_pair_conv(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
                               int64_t N, float* d_out_NM, int Mtot, int m_off);

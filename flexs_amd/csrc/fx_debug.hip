@@ -122,6 +122,33 @@ int64_t fx_debug_conv1_table(fx_model* m, float* out, int64_t cap) {
     FX_HIP(e, hipMemcpy(out, m->d_packed + lay.off_c1tab, sizeof(float) * (size_t)lay.c1tab_floats, hipMemcpyDeviceToHost));
     return lay.c1tab_floats;
 }
+// A conv2 prefix table of a model (FxPackLayout::off_c2p[depth - 1]: 3 families x 4^(4 + depth) rows of 32 floats, pre-ReLU) as it lies in device
+// memory.  Returns the number of floats copied; FX_EUNSUPPORTED: this shape has no tables; FX_EINVAL: no such depth
+int64_t fx_debug_conv2_prefix(fx_model* m, int depth, float* out, int64_t cap) {
+    if (!m || !out || depth < 1 || depth > FX_C2P_MAX_DEPTH) return FX_EINVAL;
+    fx_engine* e = m->eng;
+    const FxPackLayout& lay = m->layout;
+    if (lay.off_c2p[depth - 1] < 0) return FX_EUNSUPPORTED;
+    if (!m->has_weights) return fx_fail(e, FX_ESTATE, "model has no weights");
+    if (cap < lay.c2p_floats[depth - 1]) return FX_EINVAL;
+    FX_HIP(e, hipSetDevice(e->device));
+    FX_HIP(e, hipStreamSynchronize(e->stream));
+    FX_HIP(e, hipMemcpy(out, m->d_packed + lay.off_c2p[depth - 1], sizeof(float) * (size_t)lay.c2p_floats[depth - 1], hipMemcpyDeviceToHost));
+    return lay.c2p_floats[depth - 1];
+}
+// Host only: where the tables behind the packed image lie -- {alloc_floats, dev_floats, off_c1tab, c1tab_floats, off_c2p[0], c2p_floats[0], off_c2p[1],
+// c2p_floats[1]} -- and the row (of 32 floats) of a depth's tables that conv position p of a row with the given codes (two bits per letter) reads
+int fx_debug_table_layout(int kind, int L, int A, int F, int H, int K, int64_t* out8) {
+    if (!out8) return FX_EINVAL;
+    const FxPackLayout p = fx_pack_layout(FxShape{kind, L, A, F, H, K});
+    const int64_t v[8] = {p.alloc_floats, p.dev_floats, p.off_c1tab, p.c1tab_floats, p.off_c2p[0], p.c2p_floats[0], p.off_c2p[1], p.c2p_floats[1]};
+    std::memcpy(out8, v, sizeof(v));
+    return FX_OK;
+}
+int64_t fx_debug_conv2_prefix_row(unsigned codes, int p, int depth) {
+    if (p < 0 || p > 3 || depth < 1 || depth > FX_C2P_MAX_DEPTH) return FX_EINVAL;
+    return (int64_t)fx_c2p_row(codes, p, depth);
+}
 int fx_debug_mfma_probe(fx_engine* e, const float* a64, const float* b64, const float* c256, float* d256) {
     if (!e || !a64 || !b64 || !c256 || !d256) return FX_EINVAL;
     FX_HIP(e, hipSetDevice(e->device));

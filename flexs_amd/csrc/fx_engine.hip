@@ -322,6 +322,7 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "wave_prio")) return &e->wave_prio;
     if (!std::strcmp(key, "cnn_quad_tail")) return &e->cnn_quad_tail;
     if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
+    if (!std::strcmp(key, "cnn_conv2_prefix")) return &e->cnn_conv2_prefix;
     if (!std::strcmp(key, "cnn_head_slab")) return &e->cnn_head_slab;
     if (!std::strcmp(key, "dense_pipe")) return &e->dense_pipe;
     if (!std::strcmp(key, "fuse_mean")) return &e->fuse_mean;
@@ -383,6 +384,8 @@ static bool ab_only_value(const fx_engine* e, const int64_t* s, int64_t value) {
 int fx_engine_set_option(fx_engine* e, const char* key, int64_t value) {
     int64_t* s = option_slot(e, key);
     if (!s) return fx_fail(e, FX_EINVAL, std::string("unknown option ") + (key ? key : "(null)"));
+    if (s == &e->cnn_conv2_prefix && (value < 0 || value > FX_C2P_MAX_DEPTH))
+        return fx_fail(e, FX_EINVAL, "cnn_conv2_prefix is 0 (off) or a depth that is compiled in (1, 2)");
     if (ab_only_value(e, s, value))
         return fx_fail(e, FX_EUNSUPPORTED, std::string("option ") + key + " = " + std::to_string(value) + " selects a kernel form of the A/B build "
                        "(measured slower, see csrc/OPTIONS.md): make -C flexs_amd/csrc ab, FLEXS_AMD_LIB=.../libflexs_amd_ab.so");
@@ -415,6 +418,7 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "launch_first_calls")) { *value = e->launch_first_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_first_redone")) { *value = e->launch_first_redone; return FX_OK; }
     if (e && key && !std::strcmp(key, "conv1_table_launches")) { *value = e->counters.conv1_table_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "conv2_prefix_launches")) { *value = e->counters.conv2_prefix_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "large_bar")) { *value = (e->large_bar && !e->rows_refused) ? 1 : 0; return FX_OK; }   // (the host can store into device memory: resident forms, launched-first calls)
     if (e && key && !std::strcmp(key, "server_streamed")) { *value = e->server.streamed; return FX_OK; }
@@ -523,6 +527,7 @@ int fx_model_set_weights(fx_model* m, const float* blob, int64_t n) {
     FX_HIP(e, hipMemcpy(m->d_blob, m->blob.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     FX_HIP(e, hipMemcpy(m->d_packed, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
     if (int rc = fx_build_conv1_table(e, m)) return rc;      // (on e->stream, in front of every launch that reads it)
+    if (int rc = fx_build_conv2_prefix(e, m)) return rc;     // (reads the conv1 table: behind it on the same stream)
     m->has_weights = true;
     m->bt_valid = false;
     return FX_OK;

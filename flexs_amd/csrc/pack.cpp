@@ -97,6 +97,16 @@ FxPackLayout fx_pack_layout(const FxShape& s) {
         p.c1tab_floats = (int64_t)FX_C1T_WINDOWS * 16 * p.FT;
         p.dev_floats = p.off_c1tab + p.c1tab_floats;
     }
+    // ... and conv2's first taps per position behind it (3 x 128 KiB at depth 1, 3 x 512 KiB at depth 2): rows of 32 floats again, so every
+    // offset stays a multiple of a line
+    for (int d = 1; d <= FX_C2P_MAX_DEPTH; ++d) {
+        p.off_c2p[d - 1] = -1;
+        p.c2p_floats[d - 1] = 0;
+        if (p.off_c1tab < 0) continue;
+        p.off_c2p[d - 1] = p.dev_floats;
+        p.c2p_floats[d - 1] = (int64_t)FX_C2P_FAMILIES * FX_C2P_ENTRIES(d) * 16 * p.FT;
+        p.dev_floats += p.c2p_floats[d - 1];
+    }
     return p;
 }
 

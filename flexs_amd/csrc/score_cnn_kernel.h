@@ -49,6 +49,7 @@ struct CnnArgs {
     // packed-layout offsets (floats)
     int off_first, off_c2, off_c3, off_cb, off_w1p, conv_floats, off_d1, off_d2, off_db, total_floats;
     int off_c1tab;              // C1T: the member's conv1 table behind its packed image (FxPackLayout::off_c1tab), never staged into LDS
+    int off_c2p;                // C2P: the member's conv2 prefix tables of the launch's depth (FxPackLayout::off_c2p[C2P - 1]), never staged into LDS
     int stw_stride;             // STG: bytes of LDS scratch per wave (16 L rounded up to 16)
     int stw_ahead;              // STG: 1 = two scratches per wave, the next tile's bytes are asked for a tile ahead (fx_stage_tile_dma)
     FxRowsReady ready;          // launched-first host call: the rows arrive while the kernel runs (words == nullptr: they are all there)
@@ -118,9 +119,16 @@ __device__ __forceinline__ void fx_fused_mean_tile(float* planes, int64_t stride
 // four 10-bit window indices out of them and asks for its eight 16-byte pieces of the four table rows before the first conv2; there is no
 // conv1 gather (10 ds_read_b128, 20 packed adds, 32 integer maxima and the row addresses per position) and no code window.  The quad round
 // keeps the LDS gather.
+// C2P = 1, 2 (a form of C1T): conv2 at a position starts from its bias and adds its valid taps in ascending order, and its first C2P taps read
+// the first C2P conv1 outputs the position sees -- 4 + C2P letters.  The member carries the accumulator after those taps for every such index
+// and each of the three first-tap families (FxPackLayout::off_c2p; fx_build_conv2_prefix runs this kernel's own init_bias + mma_layer chain on
+// the conv1 table's rows: the same bits).  A tile loads its four positions' prefixes (eight 16-byte pieces) into what becomes o2, runs only the
+// remaining taps -- 64 / 128 MFMAs fewer per tile -- and no longer asks for the first C2P conv1 rows, which nothing reads any more: 14 / 12
+// loads per lane and tile, issued in the order of first use.  The quad round keeps the gather and all taps.
 template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false>
+          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false, int C2P = 0>
 __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
+    static_assert(C2P >= 0 && C2P <= FX_C2P_MAX_DEPTH && (C2P == 0 || C1T), "C2P is a form of C1T: its index is cut from C1T's codes and the remaining taps read C1T's rows");
     static_assert(!C1T || (A == 4 && K == 5 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S == 4 && !SEG && HEAD && !STG),
                   "C1T reads the table of 4^5 windows x 32 channels; the four positions of a seq_len = 8 row; built and measured in 16-wave workgroups");
     static_assert(!QT || (A == 4 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S > 0 && L1S <= 4 && !SEG && HEAD && !STG),
@@ -199,6 +207,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
         const float* cb = smem + p.off_cb;
         const float* w1p = smem + p.off_w1p;
         [[maybe_unused]] const char* c1tab = C1T ? reinterpret_cast<const char*>(p.w[m] + p.off_c1tab) : nullptr;
+        [[maybe_unused]] const char* c2ptab = C2P > 0 ? reinterpret_cast<const char*>(p.w[m] + p.off_c2p) : nullptr;
         const float* dbase = DENSE_LDS ? smem : p.w[m];
         const f4* w_d1 = reinterpret_cast<const f4*>(dbase + p.off_d1);
         const f4* w_d2 = reinterpret_cast<const f4*>(dbase + p.off_d2);
@@ -301,6 +310,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
             // code window: alphabet index at positions s .. s+K-1
             [[maybe_unused]] int cw[K][NT];
             [[maybe_unused]] f4 c1t[C1T ? L1S : 1][FT];  // C1T: conv1's outputs of the tile's positions, on their way from the table
+            [[maybe_unused]] f4 c2p[C2P > 0 ? L1S : 1][FT];   // C2P: conv2's accumulators after the tabulated taps, likewise
             if constexpr (C1T) {
                 unsigned codes = 0;                       // two bits per letter of the row
 #pragma unroll
@@ -309,12 +319,28 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
                     if (c == 0xFF) { bad = true; c = 0; }
                     codes |= c << (2 * j);
                 }
-#pragma unroll
-                for (int s = 0; s < L1S; ++s) {
+                auto ask_c1 = [&](int s) {
                     // window s = letters s .. s + 4, letter j weighs 4^j; the mask keeps the row inside the table whatever the LUT holds
                     const unsigned at = (((codes >> (2 * s)) & (unsigned)(FX_C1T_WINDOWS - 1)) << 7) | ((unsigned)g << 4);
 #pragma unroll
                     for (int mo = 0; mo < FT; ++mo) c1t[s][mo] = *reinterpret_cast<const f4*>(c1tab + at + 64 * mo);
+                };
+                if constexpr (C2P > 0) {
+                    // in the order of first use: position t's prefix, then the conv1 rows its remaining taps read that no earlier position
+                    // asked for (conv1 rows 0 .. C2P - 1 are read by tabulated taps only)
+                    int asked = C2P;
+#pragma unroll
+                    for (int t = 0; t < L1S; ++t) {
+                        const unsigned at = (fx_c2p_row(codes, t, C2P) << 7) | ((unsigned)g << 4);
+#pragma unroll
+                        for (int mo = 0; mo < FT; ++mo) c2p[t][mo] = *reinterpret_cast<const f4*>(c2ptab + at + 64 * mo);
+#pragma unroll
+                        for (int s = 0; s < L1S; ++s)
+                            if (s >= asked && s <= t + PR2) { ask_c1(s); asked = s + 1; }
+                    }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < L1S; ++s) ask_c1(s);
                 }
             } else {
 #pragma unroll
@@ -442,7 +468,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
                 if (C1T && s < L1) {
                     // (L1S > 0: s == u)
 #pragma unroll
-                    for (int t = 0; t < FT; ++t) win1[FX_W1NEW][t][0] = c1t[C1T && u < L1S ? u : 0][t];
+                    for (int t = 0; t < FT; ++t) win1[FX_W1NEW][t][0] = u >= C2P ? c1t[C1T && u < L1S ? u : 0][t] : splat4(0.f);   // (C2P: the first rows are never read)
                 } else if (s < L1 && act) {
                     f4 o1[FT][NT];
                     init_bias<FT, NT>(cb, o1, g);
@@ -493,11 +519,17 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
                 const int t2 = s - PR2;
                 if (t2 >= 0 && t2 < L1 && act) {
                     f4 o2[FT][NT];
-                    init_bias<FT, NT>(cb + 16 * FT, o2, g);
+                    int j_from = 0;
+                    if constexpr (C2P > 0) {
+                        // (L1S > 0: t2 is a constant of the unrolled step)  the bias and the first C2P valid taps come from the table
+#pragma unroll
+                        for (int t = 0; t < FT; ++t) o2[t][0] = c2p[t2 < L1S ? t2 : 0][t];
+                        j_from = fx_c2p_first_tap(t2) + C2P;
+                    } else init_bias<FT, NT>(cb + 16 * FT, o2, g);
 #pragma unroll
                     for (int j = 0; j < K; ++j) {
                         const int pp = t2 + j - PL2;
-                        if (pp >= 0 && pp < L1)            // zero padding contributes nothing
+                        if (j >= j_from && pp >= 0 && pp < L1)   // zero padding contributes nothing
                             mma_layer<FT, FT, NT, PRIO>(w_c2 + j * FT * FT * 64, win1[FX_W1(j)], o2, lane);
                     }
                     relu_tiles<FT, NT>(o2);
@@ -672,10 +704,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
 }
 
 template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false>
+          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false, int C2P = 0>
 int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     constexpr int waves = WAVES;
-    auto kern = k_score_cnn_mfma<A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT, C1T>;
+    auto kern = k_score_cnn_mfma<A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT, C1T, C2P>;
     if (QT) lds_bytes += (size_t)3 * 2 * 8 * 1024;               // three quads' exchange buffers (2 x 8 KiB each)
     if (SEG) lds_bytes += (size_t)WAVES * FT * 64 * 16;          // segment-maxima slots
     const bool ahead = STG && e->cnn_stage_host >= 2 && lds_bytes + 2 * (size_t)WAVES * ((16 * (size_t)a_in.L + 15) / 16 * 16) <= (size_t)e->max_lds;
@@ -709,6 +741,7 @@ int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), lds_bytes, e->stream, a);
     FX_HIP(e, hipGetLastError());
     if (C1T) e->counters.conv1_table_launches += 1;
+    if (C2P > 0) e->counters.conv2_prefix_launches += 1;
 #if defined(FX_AB)
     if (a.fm_mean) e->fused_mean_done = true;
 #endif

@@ -62,11 +62,18 @@ int dispatch_a4(fx_engine* e, const CnnArgs& a0, int variant, bool big, size_t f
                     // rows arrive while the kernel runs (the table's second round trip would stand behind the wait for the rows)
                     {
                         const bool c1t = e->cnn_conv1_table && !e->rows_req.on && a.off_c1tab >= 0;
+                        // ... and conv2's first one or two taps per position read from the member's prefix tables (cnn_conv2_prefix; a form of
+                        // the table form: every other launch silently runs all taps)
+                        const int c2p = c1t && a.off_c2p >= 0 ? (int)e->cnn_conv2_prefix : 0;
                         if (e->cnn_quad_tail && !e->rows_req.on && lds + (size_t)3 * 2 * 8 * 1024 <= (size_t)e->max_lds) {
                             a.quad_tail = 1;
+                            if (c2p == 1) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true, true, 1>(e, a, lds);
+                            if (c2p == 2) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true, true, 2>(e, a, lds);
                             if (c1t) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true, true>(e, a, lds);
                             return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, true>(e, a, lds);
                         }
+                        if (c2p == 1) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, false, true, 1>(e, a, lds);
+                        if (c2p == 2) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, false, true, 2>(e, a, lds);
                         if (c1t) return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true, false, true, false, false, true>(e, a, lds);
                     }
                     return launch_g<4, 5, 2, 7, 1, true, 16, true, 4, true>(e, a, lds);
@@ -141,7 +148,53 @@ __global__ void __launch_bounds__(256) k_build_conv1_table(const float* packed, 
     *reinterpret_cast<f4*>(tab + w * 32 + 4 * q) = relu4(o);
 }
 
+// The conv2 prefix tables of one member (C2P): one wave per 16 entries, lane (g, sq) = entry sq of the 16, channels 16 mo + 4 g + r -- the
+// accumulator layout of a tile whose 16 sequences are the 16 entries.  The chain is the scoring kernel's: init_bias on the conv2 bias, then
+// mma_layer<2, 2, 1> for tap j0 (and j0 + 1 at depth 2) over the packed conv2 blocks, with the conv1 table's row of the entry's window as the B
+// operand in the (mi, r) order of a tile's win1 -- so every accumulator sees the MFMAs it sees in the full walk (a column of an MFMA depends on
+// no other column) and the stored pre-ReLU bits are those a tile holds after its first taps.
+template <int DEPTH>
+__device__ __forceinline__ void fx_c2p_build_entries(const float* packed, int off_cb, int off_c2, const float* c1tab, float* tab, int j0, int idx,
+                                                     int lane, int g) {
+    f4 acc[2][1];
+    init_bias<2, 1>(packed + off_cb + 16 * 2, acc, g);
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+        const int w = (idx >> (2 * d)) & (FX_C1T_WINDOWS - 1);       // window d of the entry = letters d .. d + 4
+        f4 in[2][1];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) in[mi][0] = *reinterpret_cast<const f4*>(c1tab + w * 32 + 16 * mi + 4 * g);
+        mma_layer<2, 2, 1>(reinterpret_cast<const f4*>(packed + off_c2) + (j0 + d) * 2 * 2 * 64, in, acc, lane);
+    }
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+        *reinterpret_cast<f4*>(tab + ((int64_t)j0 * FX_C2P_ENTRIES(DEPTH) + idx) * 32 + 16 * mo + 4 * g) = acc[mo][0];
+}
+constexpr int FX_C2P_WAVES1 = FX_C2P_FAMILIES * FX_C2P_ENTRIES(1) / 16, FX_C2P_WAVES2 = FX_C2P_FAMILIES * FX_C2P_ENTRIES(2) / 16;
+static_assert(FX_C2P_MAX_DEPTH == 2 && (FX_C2P_WAVES1 + FX_C2P_WAVES2) % 4 == 0, "k_build_conv2_prefix: both depths in one grid of whole 4-wave workgroups");
+__global__ void __launch_bounds__(256) k_build_conv2_prefix(float* packed, int off_cb, int off_c2, int off_c1tab, int off_t1, int off_t2) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, sq = lane & 15;
+    int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));   // the grid is exactly FX_C2P_WAVES1 + FX_C2P_WAVES2 waves
+    if (wave < FX_C2P_WAVES1) {
+        constexpr int per = FX_C2P_ENTRIES(1) / 16;
+        fx_c2p_build_entries<1>(packed, off_cb, off_c2, packed + off_c1tab, packed + off_t1, wave / per, (wave % per) * 16 + sq, lane, g);
+    } else {
+        wave -= FX_C2P_WAVES1;
+        constexpr int per = FX_C2P_ENTRIES(2) / 16;
+        fx_c2p_build_entries<2>(packed, off_cb, off_c2, packed + off_c1tab, packed + off_t2, wave / per, (wave % per) * 16 + sq, lane, g);
+    }
+}
+
 }  // namespace
+
+int fx_build_conv2_prefix(fx_engine* e, fx_model* m) {
+    const FxPackLayout& lay = m->layout;
+    if (lay.off_c1tab < 0 || lay.off_c2p[0] < 0 || lay.off_c2p[1] < 0) return FX_OK;
+    hipLaunchKernelGGL(k_build_conv2_prefix, dim3((FX_C2P_WAVES1 + FX_C2P_WAVES2) / 4), dim3(256), 0, e->stream, m->d_packed, (int)lay.off_cb,
+                       (int)lay.off_c2, (int)lay.off_c1tab, (int)lay.off_c2p[0], (int)lay.off_c2p[1]);
+    FX_HIP(e, hipGetLastError());
+    return FX_OK;
+}
 
 int fx_build_conv1_table(fx_engine* e, fx_model* m) {
     const FxPackLayout& lay = m->layout;
@@ -186,6 +239,7 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
     a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
     a.off_c1tab = (int)lay.off_c1tab;
+    a.off_c2p = e->cnn_conv2_prefix >= 1 && e->cnn_conv2_prefix <= FX_C2P_MAX_DEPTH ? (int)lay.off_c2p[e->cnn_conv2_prefix - 1] : -1;
 
 #if defined(FX_AB)
     // mean-only call with the rows resident in device memory and every member in this launch: the last member to finish a tile averages

@@ -463,6 +463,16 @@ int64_t fx_debug_packed_size(int kind, int L, int A, int F, int H, int K);
  * floats, row w = sum_j code[j] * 4^j, channel order as packed) as the device built it at fx_model_set_weights.  Returns the
  * number of floats copied (cap must hold 32768), FX_EUNSUPPORTED for shapes without a table. */
 int64_t fx_debug_conv1_table(fx_model *m, float *out, int64_t cap);
+/* Needs the GPU: a conv2 prefix table of such a model (depth 1 or 2: conv2's accumulator, pre-ReLU, after the first `depth` valid
+ * taps; 3 first-tap families x 4^(4 + depth) rows of 32 floats, row index = sum_i code[i] * 4^i) as the device built it at
+ * fx_model_set_weights.  Returns the number of floats copied (cap must hold 98304 / 393216), FX_EUNSUPPORTED for shapes without
+ * tables, FX_EINVAL for any other depth. */
+int64_t fx_debug_conv2_prefix(fx_model *m, int depth, float *out, int64_t cap);
+/* Host only: {alloc_floats, dev_floats, off_c1tab, c1tab_floats, off_c2p[0], c2p_floats[0], off_c2p[1], c2p_floats[1]} of the
+ * device buffer of a model of this shape (floats; offsets -1 and sizes 0 where the shape carries no table), and the row of a
+ * depth's prefix tables that conv position p (0..3) of a seq_len = 8 row reads (codes: two bits per letter, letter i at bits 2i). */
+int fx_debug_table_layout(int kind, int L, int A, int F, int H, int K, int64_t *out8);
+int64_t fx_debug_conv2_prefix_row(unsigned codes, int p, int depth);
 int fx_debug_pack_layout(int kind, int L, int A, int F, int H, int K, int64_t *out16);
 /* v_mfma_f32_16x16x4_f32 instructions (2048 FLOP each) the MFMA scoring kernels issue per 16-sequence tile per
  * member for this shape -- the kernels' loop bounds restated on the host ('same'-padding taps and the one-hot
