@@ -828,6 +828,26 @@ def debug_pack_layout(kind, L, A, F, H, K) -> dict:
     return dict(zip(names, list(v)))
 
 
+CNN_FORM_FIELDS = ["A", "K", "FT", "HT", "NT", "DENSE_LDS", "WAVES", "G1", "L1S", "PRIO", "SEG", "HEAD", "STG", "QT", "C1T", "C2P"]
+
+
+def debug_cnn_form_pick(L, A, F, H, K, N, M, *, path=0, num_cus=256, max_lds=160 * 1024, rows_on=False, ascii_host=False,
+                        options=None) -> dict:
+    """Which form of the fused CNN kernel a launch gets, and its geometry (host only; path 1: the conv part of the two-kernel
+    path).  Keys: the form's fields, TG, seg_sb, lds, id, pair_first, ab_build, and rc / msg: the launcher's status."""
+    options = dict(options or {})
+    keys = (C.c_char_p * max(len(options), 1))(*[k.encode() for k in options])
+    vals = (C.c_int64 * max(len(options), 1))(*options.values())
+    v = (C.c_int64 * 24)()
+    msg = C.create_string_buffer(256)
+    rc = lib().fx_debug_cnn_form_pick(path, L, A, F, H, K, N, M, num_cus, max_lds, int(rows_on), int(ascii_host), keys, vals,
+                                      len(options), v, msg, len(msg))
+    out = dict(zip(CNN_FORM_FIELDS + ["TG", "seg_sb", "lds", "id", "pair_first", "ab_build"], list(v)))
+    out["rc"] = status_name(rc)
+    out["msg"] = msg.value.decode()
+    return out
+
+
 def debug_table_layout(kind, L, A, F, H, K) -> dict:
     """Where the device-built tables lie behind the packed image (floats; -1 / 0: the shape has none)."""
     v = (C.c_int64 * 8)()

@@ -8,6 +8,7 @@
 #include "fx_internal.h"
 #include "myers.h"
 #include "np_sum.h"
+#include "score_cnn_forms.h"
 #include <atomic>
 #include <mutex>
 #include <chrono>
@@ -100,6 +101,36 @@ int fx_debug_pack_layout(int kind, int L, int A, int F, int H, int K, int64_t* o
                            p.off_d1, p.off_d2, p.off_d3, p.off_db, p.RLH, p.total_floats, p.off_w1p, p.HTR};
     std::memcpy(out16, v, sizeof(v));
     return FX_OK;
+}
+// Host only: the form of the fused CNN kernel (path 0: score_cnn_mfma.hip; 1: the conv part of score_cnn_split.hip) and the launch geometry that a
+// launch of M members of CNN(F, H, K) on N sequences would get from an engine with these properties and option overrides -- the launchers' own
+// pure functions (score_cnn_forms.h) on a default engine that never sees a device.  out24 = the sixteen form fields in the order of
+// fx_cnn_form_fields, TG, seg_sb, LDS bytes, CnnFormId, pair_first, 1 in the A/B build.  Returns the status the launcher would return after
+// score_cnn_quad.hip / score_cnn_pair.hip declined (its message, if any, in msg), or the status fx_engine_set_option has for an override.
+int fx_debug_cnn_form_pick(int path, int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host,
+                           const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out24, char* msg, int msg_cap) {
+    if (!out24 || path < 0 || path > 1 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
+    fx_engine eng;
+    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    std::memset(out24, 0, 24 * sizeof(int64_t));
+    if (msg && msg_cap > 0) msg[0] = 0;
+    auto say = [&](const char* text) { if (msg && msg_cap > 0 && text) std::snprintf(msg, (size_t)msg_cap, "%s", text); };
+    for (int i = 0; i < n_opts; ++i) {
+        int64_t* slot = nullptr;
+        if (int rc = fx_option_slot_for(&eng, opt_keys[i], opt_values[i], &slot)) { say(eng.last_error.c_str()); return rc; }
+        *slot = opt_values[i];
+    }
+    const FxShape s{FX_CNN, L, A, F, H, K};
+    const FxPackLayout lay = fx_pack_layout(s);
+    const CnnPick pk = path == 0 ? fx_cnn_pick_fused(&eng, s, lay, N, M) : fx_cnn_pick_conv(&eng, s, lay, N, M);
+    out24[16] = pk.TG; out24[17] = pk.seg_sb; out24[18] = (int64_t)pk.lds; out24[19] = pk.id; out24[20] = pk.pair_first;
+#if defined(FX_AB)
+    out24[21] = 1;
+#endif
+    say(pk.msg);
+    if (pk.rc || pk.id == CNN_NO_FORM) return pk.rc;
+    auto fields = [&](auto form) { fx_cnn_form_fields<decltype(form)>(out24); return (int)FX_OK; };
+    return path == 0 ? fx_cnn_with_fused_form(pk, fields) : fx_cnn_with_conv_form(pk, fields);
 }
 int fx_debug_pack_weights(int kind, int L, int A, int F, int H, int K, const float* blob, int64_t n, float* packed,
                           int64_t cap) {

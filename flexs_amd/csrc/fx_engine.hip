@@ -381,7 +381,7 @@ static bool ab_only_value(const fx_engine* e, const int64_t* s, int64_t value) {
 #endif
 }
 
-int fx_engine_set_option(fx_engine* e, const char* key, int64_t value) {
+int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** slot) {
     int64_t* s = option_slot(e, key);
     if (!s) return fx_fail(e, FX_EINVAL, std::string("unknown option ") + (key ? key : "(null)"));
     if (s == &e->cnn_conv2_prefix && (value < 0 || value > FX_C2P_MAX_DEPTH))
@@ -389,6 +389,13 @@ int fx_engine_set_option(fx_engine* e, const char* key, int64_t value) {
     if (ab_only_value(e, s, value))
         return fx_fail(e, FX_EUNSUPPORTED, std::string("option ") + key + " = " + std::to_string(value) + " selects a kernel form of the A/B build "
                        "(measured slower, see csrc/OPTIONS.md): make -C flexs_amd/csrc ab, FLEXS_AMD_LIB=.../libflexs_amd_ab.so");
+    *slot = s;
+    return FX_OK;
+}
+
+int fx_engine_set_option(fx_engine* e, const char* key, int64_t value) {
+    int64_t* s = nullptr;
+    if (int rc = fx_option_slot_for(e, key, value, &s)) return rc;
     // a running resident generation was started under the old options (its geometry, but also the kernel forms its
     // workgroups run: pair rows or plain rows, ...): it leaves, the next calls start a new one under the new ones
     if (*s != value) { fx_server_stop(e); lp_disarm(e); }

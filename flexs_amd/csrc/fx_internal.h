@@ -20,6 +20,7 @@ static inline int64_t planar_stride_for(int64_t N) { return (N + 63) & ~(int64_t
 
 extern "C" {
 FXI int check_deferred(fx_engine* e);      // fx_engine.hip
+FXI int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** slot);      // fx_engine.hip: where option `key` lives, after fx_engine_set_option's refusals of `value`
 FXI int fx_zero_copy_buffers(fx_engine* e, size_t in_bytes, size_t out_bytes, FxZeroCopy* z);      // fx_engine.hip
 FXI int fx_wait_small(fx_engine* e);      // fx_resident.hip
 FXI void host_mean_planes(const float* pl, int64_t stride, int64_t N, int M, float* out_mean);      // fx_resident.hip

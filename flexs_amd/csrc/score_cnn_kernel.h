@@ -13,11 +13,14 @@
 // Algorithmic work per sequence per member: L + 4 bytes of HBM
 // traffic, 2 * MACs FLOP with MACs = L1*K*A*F + L1*K*F*F + L1*(A-1)*F*F + F*H + H*H + H.
 // The kernel is f32-MFMA-bound (157.3 TFLOP/s peak), not HBM-bound.
-// The fused CNN scoring kernel template (shared by score_cnn_mfma.hip, which instantiates the fused forms, and
-// score_cnn_split.hip, which instantiates the conv-only form for non-canonical shapes).
+//
+// This header is the kernel template and its launcher, shared by score_cnn_mfma.hip, which instantiates the fused forms, and
+// score_cnn_split.hip, which instantiates the conv-only forms for non-canonical shapes; the forms are named, and one is chosen, in
+// score_cnn_forms.h.  What a form's fields mean: the comment in front of the kernel.
 #pragma once
 #include "fx_common.h"
 #include "mfma_common.h"
+#include "score_cnn_forms.h"
 #include "score_cnn_quad_round.h"
 #include "np_sum.h"
 
@@ -97,15 +100,37 @@ __device__ __forceinline__ void fx_fused_mean_tile(float* planes, int64_t stride
 #define FX_FM_ON(p) false
 #endif
 
+// The kernel is a template over ONE type, the form (score_cnn_forms.h: CnnForm carries the defaults, a named form shadows what it changes), whose
+// fields it binds once at its top.  The fields:
+//
+// A, K: alphabet size and kernel size of conv1 / conv2 (conv3's is A - 1).
+//
+// FT, HT: 16-channel tiles of the filters (1 or 2) and of the hidden units (FxPackLayout::HT: rounded up to an instantiated count).
+//
+// NT: tiles of 16 sequences per wave (2: A/B build only, measured slower).
+//
+// DENSE_LDS: the whole member sits in LDS; false: only the conv part does and the dense head's weights stream from L2.
+//
+// WAVES: waves per workgroup -- 16 (four per SIMD, 128 registers) for long launches, 8 (256 registers), 4 (one per SIMD).
+//
+// G1: the one-hot conv1 as an LDS gather of kernel rows + VALU adds; false: on MFMA (A/B build only, 3-15 % slower).
+//
 // L1S > 0: number of conv positions known at compile time (L1S = seq_len - K + 1): the position loop is fully
 // unrolled, so the sliding windows become register renames instead of v_mov chains and the padding tests fold.
+//
+// PRIO: s_setprio around the MFMA clusters (mma_layer) -- with the unrolled forms, +2-5 %.
+//
 // SEG: small batches (fewer tiles than CUs) -- the WAVES waves of a workgroup share ONE tile and split its conv
 // positions: wave q streams segment q plus a halo of PL3 + PL2 positions before and PR2 + PR3 after it, pools
 // only its own positions (every conv3 output sees the same MFMA sequence as in the whole-sequence walk, so the
 // result is bit-identical), the segment maxima meet in LDS and wave 0 runs the dense head.
+//
 // HEAD = false: the conv part only -- the global max-pooled features of every tile go to `pool_out` in accumulator
 // (= B-operand) layout and a separate head kernel (score_cnn_split.hip) finishes the sequence.  Used for the CNN
 // shapes whose (kernel size, hidden width) pair has no fused instantiation.
+//
+// STG: the sequences lie in host memory; a tile's bytes are copied into the wave's LDS scratch first (the comment at `stw` below).
+//
 // QT (round 6; the unrolled seq_len = 8 form in 16-wave workgroups): 18.31 tiles per SIMD on the 3 x 1e5 headline launch mean that a SIMD
 // with a 19th tile sets the launch (in-kernel timeline profiles/r6_trace_probe.json: workgroups of 72 tiles leave at 175 us, those of 73 / 74
 // at 192 us).  The (tiles mod 4) last tiles of a workgroup are left out of the per-SIMD shares and walked by wave QUADS -- one wave per SIMD,
@@ -113,21 +138,25 @@ __device__ __forceinline__ void fx_fused_mean_tile(float* planes, int64_t stride
 // Measured with it and NOT kept: a staged start (image by direct global -> LDS copies in two parts, every wave's first row asked for ahead of
 // the copies, first tiles start when the 35 KiB conv part has landed, the head part awaited through an LDS count) -- 1.5 % SLOWER on the
 // headline launch and on a one-member launch (profiles/r6_dma_start_ab.log; tools/archive/runs/r6_dma_start_ab.py).
+//
 // C1T (the unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts): conv1's output at a position is a function
 // of five letters of a four-letter alphabet, so the member carries all 4^5 of them as a table behind its packed image (fx_build_conv1_table:
 // the gather's own adds and ReLU, the same bits).  A tile turns its row into codes through the LUT as before (same bad-character rule), cuts
 // four 10-bit window indices out of them and asks for its eight 16-byte pieces of the four table rows before the first conv2; there is no
 // conv1 gather (10 ds_read_b128, 20 packed adds, 32 integer maxima and the row addresses per position) and no code window.  The quad round
 // keeps the LDS gather.
+//
 // C2P = 1, 2 (a form of C1T): conv2 at a position starts from its bias and adds its valid taps in ascending order, and its first C2P taps read
 // the first C2P conv1 outputs the position sees -- 4 + C2P letters.  The member carries the accumulator after those taps for every such index
 // and each of the three first-tap families (FxPackLayout::off_c2p; fx_build_conv2_prefix runs this kernel's own init_bias + mma_layer chain on
 // the conv1 table's rows: the same bits).  A tile loads its four positions' prefixes (eight 16-byte pieces) into what becomes o2, runs only the
 // remaining taps -- 64 / 128 MFMAs fewer per tile -- and no longer asks for the first C2P conv1 rows, which nothing reads any more: 14 / 12
 // loads per lane and tile, issued in the order of first use.  The quad round keeps the gather and all taps.
-template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false, int C2P = 0>
-__global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
+template <class Form>
+__global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
+    constexpr int A = Form::A, K = Form::K, FT = Form::FT, HT = Form::HT, NT = Form::NT, WAVES = Form::WAVES, L1S = Form::L1S, C2P = Form::C2P;
+    constexpr bool DENSE_LDS = Form::DENSE_LDS, G1 = Form::G1, PRIO = Form::PRIO, SEG = Form::SEG, HEAD = Form::HEAD, STG = Form::STG, QT = Form::QT,
+                   C1T = Form::C1T;
     static_assert(C2P >= 0 && C2P <= FX_C2P_MAX_DEPTH && (C2P == 0 || C1T), "C2P is a form of C1T: its index is cut from C1T's codes and the remaining taps read C1T's rows");
     static_assert(!C1T || (A == 4 && K == 5 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S == 4 && !SEG && HEAD && !STG),
                   "C1T reads the table of 4^5 windows x 32 channels; the four positions of a seq_len = 8 row; built and measured in 16-wave workgroups");
@@ -703,11 +732,11 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
     if (bad) fx_raise(p.err, FX_ERR_BADCHAR);
 }
 
-template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES, bool G1, int L1S = 0, bool PRIO = false,
-          bool SEG = false, bool HEAD = true, bool STG = false, bool QT = false, bool C1T = false, int C2P = 0>
+template <class Form>
 int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
-    constexpr int waves = WAVES;
-    auto kern = k_score_cnn_mfma<A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT, C1T, C2P>;
+    constexpr int FT = Form::FT, NT = Form::NT, WAVES = Form::WAVES, C2P = Form::C2P, waves = WAVES;
+    constexpr bool SEG = Form::SEG, HEAD = Form::HEAD, STG = Form::STG, QT = Form::QT, C1T = Form::C1T;
+    auto kern = k_score_cnn_mfma<Form>;
     if (QT) lds_bytes += (size_t)3 * 2 * 8 * 1024;               // three quads' exchange buffers (2 x 8 KiB each)
     if (SEG) lds_bytes += (size_t)WAVES * FT * 64 * 16;          // segment-maxima slots
     const bool ahead = STG && e->cnn_stage_host >= 2 && lds_bytes + 2 * (size_t)WAVES * ((16 * (size_t)a_in.L + 15) / 16 * 16) <= (size_t)e->max_lds;
@@ -746,14 +775,6 @@ int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     if (a.fm_mean) e->fused_mean_done = true;
 #endif
     return FX_OK;
-}
-
-template <int A, int K, int FT, int HT, int NT, bool DENSE_LDS, int WAVES>
-int launch_inst(fx_engine* e, const CnnArgs& a, size_t lds_bytes) {
-#if defined(FX_AB)   // (the MFMA form of the one-hot conv1 -- 3-15 % slower than the LDS gather -- lives in the A/B build, `make ab`)
-    if (e->cnn_conv1_mfma) return launch_g<A, K, FT, HT, NT, DENSE_LDS, WAVES, false>(e, a, lds_bytes);
-#endif
-    return launch_g<A, K, FT, HT, NT, DENSE_LDS, WAVES, true>(e, a, lds_bytes);
 }
 
 }  // namespace

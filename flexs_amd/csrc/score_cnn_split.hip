@@ -179,43 +179,6 @@ int dispatch_head(fx_engine* e, const HeadArgs& a, int HT) {
     }
 }
 
-template <int K, int FT>
-int launch_conv(fx_engine* e, const CnnArgs& a, size_t lds) {
-    // conv part only: one tile per wave, 8 waves, conv weights in LDS, first layer in gather form
-    if constexpr (K * 3 <= 16) {
-        // small batch of long sequences (an explorer's 1-100 sequence call): the 8 waves of a workgroup split one
-        // tile's positions, as in the fused kernel (score_cnn_mfma.hip) -- bit-identical to the one-wave walk
-        const int L1 = a.L - K + 1;
-        const bool seg = e->cnn_seg != 0 && (int64_t)a.M * a.TG <= e->num_cus && (e->cnn_seg > 0 || L1 >= 24) &&
-                         lds + (size_t)8 * FT * 64 * 16 <= (size_t)e->max_lds;
-        if (seg) return launch_g<4, K, FT, 1, 1, false, 8, true, 0, false, true, false>(e, a, lds);
-    }
-    if constexpr (K == 5 && FT == 2) {
-        // batch launches (the wide-head path, round 6): four waves per SIMD, and the unrolled walk of the canonical short landscape
-        if ((int64_t)a.M * a.TG >= (int64_t)e->num_cus * 16 && !e->rows_req.on) {
-            if (a.L == 8) return launch_g<4, 5, 2, 1, 1, false, 16, true, 4, true, false, false>(e, a, lds);
-            return launch_g<4, 5, 2, 1, 1, false, 16, true, 0, false, false, false>(e, a, lds);
-        }
-    }
-    return launch_g<4, K, FT, 1, 1, false, 8, true, 0, false, false, false>(e, a, lds);
-}
-
-template <int FT>
-int dispatch_conv(fx_engine* e, const CnnArgs& a, size_t lds, int K) {
-    switch (K) {
-        case 2: return launch_conv<2, FT>(e, a, lds);
-        case 3: return launch_conv<3, FT>(e, a, lds);
-        case 4: return launch_conv<4, FT>(e, a, lds);
-        case 5: return launch_conv<5, FT>(e, a, lds);
-        default: break;
-    }
-    if constexpr (FT <= 2) {                 // (3-4 channel tiles: the 6- and 7-tap windows do not fit the register file)
-        if (K == 6) return launch_conv<6, FT>(e, a, lds);
-        if (K == 7) return launch_conv<7, FT>(e, a, lds);
-    }
-    return FX_EUNSUPPORTED;
-}
-
 template <typename Args, typename Fn1, typename Fn2, typename Fn3, typename Fn4>
 int by_channel_tiles(int FT, Fn1 f1, Fn2 f2, Fn3 f3, Fn4 f4_) {
     switch (FT) {
@@ -238,12 +201,7 @@ int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, cons
         const FxShape& t = models[m]->shape;
         if (t.kind != FX_CNN || t.L != s.L || t.A != s.A || t.F != s.F || t.H != s.H || t.K != s.K) return FX_EUNSUPPORTED;
     }
-    // (binary alphabet, sequence_utils.py:16's BA: the canonical conv shape only -- its fused kernel covers 97..112 hidden units, this path the rest)
-    if ((s.A != 4 && s.A != 20 && s.A != 2) || lay.FT < 1 || lay.FT > 4 || s.K < 2 || s.K > 7 || s.H > 256 || M > FX_MAX_M ||
-        e->cnn_conv1_mfma || (s.A == 20 && (lay.FT != 2 || !e->cnn_pair)) || (s.A == 2 && (lay.FT != 2 || s.K != 5)))
-        return FX_EUNSUPPORTED;
-    const size_t conv_lds = (size_t)lay.conv_floats * 4 + 256 + 48;
-    if (s.A != 20 && conv_lds > (size_t)e->max_lds) return FX_EUNSUPPORTED;
+    if (int rc = fx_cnn_split_supported(e, s, lay, M)) return rc;
     const int64_t TG = (N + 15) / 16;
     void* pool = nullptr;
     int rc = fx_scratch(e, 2, (size_t)M * (size_t)TG * lay.FT * 64 * sizeof(f4), &pool);
@@ -270,10 +228,9 @@ int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, cons
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
     a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
     a.pool_out = (f4*)pool;
-    if (s.A == 2) rc = launch_g<2, 5, 2, 1, 1, false, 8, true, 0, false, false, false>(e, a, conv_lds);
-    else rc = by_channel_tiles<CnnArgs>(lay.FT, [&] { return dispatch_conv<1>(e, a, conv_lds, s.K); }, [&] { return dispatch_conv<2>(e, a, conv_lds, s.K); },
-                                        [&] { return dispatch_conv<3>(e, a, conv_lds, s.K); }, [&] { return dispatch_conv<4>(e, a, conv_lds, s.K); });
-    if (rc) return rc;
+    const CnnPick pk = fx_cnn_pick_conv(e, s, lay, N, M);    // the conv-only form of the fused kernel (score_cnn_forms.h)
+    if (pk.rc) return pk.rc;
+    if ((rc = fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, a, pk.lds); }))) return rc;
 
     HeadArgs h{};
     h.pool = (const f4*)pool; h.out = d_out_NM; h.N = N; h.TG = TG; h.M = M; h.m_off = m_off;

@@ -474,6 +474,17 @@ int64_t fx_debug_conv2_prefix(fx_model *m, int depth, float *out, int64_t cap);
 int fx_debug_table_layout(int kind, int L, int A, int F, int H, int K, int64_t *out8);
 int64_t fx_debug_conv2_prefix_row(unsigned codes, int p, int depth);
 int fx_debug_pack_layout(int kind, int L, int A, int F, int H, int K, int64_t *out16);
+/* Host only: which form of the fused CNN kernel a launch of M members of CNN(F filters, H hidden, kernel K) on N sequences of
+ * length L over A letters gets (path 0: the fused kernel; 1: the conv part of the two-kernel path), from an engine with num_cus
+ * CUs, max_lds bytes of LDS, rows arriving while the kernel runs (rows_on) or lying in host memory (ascii_host), and the n_opts
+ * engine options opt_keys[i] = opt_values[i]; every other option at its default.  No device is touched.  out24: the form's fields
+ * A, K, FT, HT, NT, DENSE_LDS, WAVES, G1, L1S, PRIO, SEG, HEAD, STG, QT, C1T, C2P, then TG, seg_sb, LDS bytes, the form's id,
+ * "the protein kernel is tried first", "this is the A/B build".  Returns what the launcher returns once the small-launch and
+ * protein kernels have declined (FX_OK, FX_EUNSUPPORTED, FX_EINVAL with its text in msg), or fx_engine_set_option's status for
+ * an override it refuses. */
+int fx_debug_cnn_form_pick(int path, int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on,
+                           int ascii_host, const char *const *opt_keys, const int64_t *opt_values, int n_opts, int64_t *out24,
+                           char *msg, int msg_cap);
 /* v_mfma_f32_16x16x4_f32 instructions (2048 FLOP each) the MFMA scoring kernels issue per 16-sequence tile per
  * member for this shape -- the kernels' loop bounds restated on the host ('same'-padding taps and the one-hot
  * first layers are not issued, the hidden tail tile runs only its real k-steps).  bench.py prices the ISSUED
