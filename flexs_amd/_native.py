@@ -669,6 +669,26 @@ class NativeModel:
         assert n == out.size
         return out
 
+    def debug_pool_table(self) -> np.ndarray:
+        """(65536, 32) global-max-pooled conv features per seq_len = 8 row (row = sum_j code[j] * 4^j) as the device built them for the
+        current weights (fx_debug_pool_table; test hook; FxError while no fresh table exists)."""
+        out = np.empty((4 ** 8, 32), np.float32)
+        n = self.engine._lib.fx_debug_pool_table(self.handle, out.ctypes.data_as(_f32p), out.size)
+        if n < 0:
+            _raise(int(n), self.engine.handle)
+        assert n == out.size
+        return out
+
+    def debug_conv_features(self, rows: np.ndarray, lut: np.ndarray) -> np.ndarray:
+        """(N, 16 * filter tiles) pooled conv features of the (N, L) uint8 rows as the conv-only kernel of the two-kernel CNN path leaves
+        them (fx_debug_cnn_conv_features; test hook)."""
+        rows = np.ascontiguousarray(rows, np.uint8)
+        lut = np.ascontiguousarray(lut, np.uint8)
+        out = np.empty((rows.shape[0], 16 * ((self.F + 15) // 16)), np.float32)
+        self.engine.check(self.engine._lib.fx_debug_cnn_conv_features(self.handle, rows.ctypes.data_as(_u8p), rows.shape[0], lut.ctypes.data_as(_u8p),
+                                                                      out.ctypes.data_as(_f32p), out.size))
+        return out
+
     def get_blob(self) -> np.ndarray:
         blob = np.empty(self.num_params, np.float32)
         self.engine.check(self.engine._lib.fx_model_get_weights(self.handle, blob.ctypes.data_as(_f32p), blob.shape[0]))
@@ -846,6 +866,24 @@ def debug_cnn_form_pick(L, A, F, H, K, N, M, *, path=0, num_cus=256, max_lds=160
     out["rc"] = status_name(rc)
     out["msg"] = msg.value.decode()
     return out
+
+
+POOL_DECISIONS = ["conv", "table", "build"]
+
+
+def debug_cnn_pool_pick(L, A, F, H, K, N, M, *, fresh, num_cus=256, max_lds=160 * 1024, rows_on=False, ascii_host=False, options=None) -> dict:
+    """What a launch group does about the members' pooled-feature tables (engine option cnn_pool_table; host only).  Keys: decision
+    ("conv": the picked conv form is launched, "table": the head-only kernel, "build": the stale tables are built first), id (the
+    pick's form id), canonical (the shape may carry a table), rc (the pick's status)."""
+    options = dict(options or {})
+    keys = (C.c_char_p * max(len(options), 1))(*[k.encode() for k in options])
+    vals = (C.c_int64 * max(len(options), 1))(*options.values())
+    v = (C.c_int64 * 4)()
+    rc = lib().fx_debug_cnn_pool_pick(L, A, F, H, K, N, M, num_cus, max_lds, int(rows_on), int(ascii_host), int(fresh), keys, vals,
+                                      len(options), v)
+    if rc != FX_OK:
+        raise ValueError(status_name(rc))
+    return {"decision": POOL_DECISIONS[v[0]], "id": int(v[1]), "canonical": bool(v[2]), "rc": status_name(int(v[3]))}
 
 
 def debug_table_layout(kind, L, A, F, H, K) -> dict:

@@ -116,6 +116,9 @@ struct FxPackLayout {
 #ifndef FX_C2P_DEFAULT
 #define FX_C2P_DEFAULT 2        // engine option cnn_conv2_prefix as shipped: the depth with the best bench.py median (profiles/conv2_prefix_ab.log; -DFX_C2P_DEFAULT=0 / 1 on fx_engine.hip: the A/B arms of bench.py)
 #endif
+#ifndef FX_POOL_TABLE_DEFAULT
+#define FX_POOL_TABLE_DEFAULT 1 // engine option cnn_pool_table as shipped (profiles/pool_table_ab.log; -DFX_POOL_TABLE_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
+#endif
 #define FX_C2P_FAMILIES 3       // first valid taps j0 = 0, 1, 2 of the four conv positions of a seq_len = 8 row
 #define FX_C2P_ENTRIES(depth) (1 << (2 * (4 + (depth))))   // 4^5 rows per family at depth 1, 4^6 at depth 2
 // conv2 ('same', five taps, tap j reads out1[p + j - 2]) at position p of the four conv positions: its first valid tap, the window that tap reads
@@ -209,6 +212,8 @@ struct fx_engine {
         int64_t pair_evals = 0;        // (query, cache entry) distance evaluations
         int64_t train_steps = 0;       // mini-batch steps x members run by fx_train_fit
         int64_t conv1_table_launches = 0;   // K1 launches that took the conv1-table form (read: option "conv1_table_launches")
+        int64_t pool_table_launches = 0;    // launch groups answered by the head-only kernel from the members' pooled-feature tables (read: option "pool_table_launches")
+        int64_t pool_table_builds = 0;      // pooled-feature tables built, one per member and build (read: option "pool_table_builds")
         int64_t conv2_prefix_launches = 0;  // ... and, of those, the ones that read conv2's first taps from the prefix tables (read: option "conv2_prefix_launches")
     } counters;
     // deferred error word (device) + pinned host mirror
@@ -253,6 +258,7 @@ struct fx_engine {
                                 // once per lockstep round of 8 tiles (k_cnn_head_slab) instead of the fused kernel, whose waves stream it from L2 per tile; 0 = the fused kernel (rounds 1-5)
     int64_t cnn_conv1_table = 1; // K1, unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts: 1 = conv1's four outputs of a tile are READ from the member's table of all 4^5 windows (FxPackLayout::off_c1tab; eight 16-byte global loads per lane and tile) instead of gathered from LDS and summed; 0 = the gather (rounds 1-6: A/B).  Same bits
     int64_t cnn_conv2_prefix = FX_C2P_DEFAULT; // K1, the conv1-table form (cnn_conv1_table = 1, rows resident, a member with tables): 1 / 2 = a tile READS conv2's accumulator after the first one / two valid taps of each of its four positions from the member's prefix tables (FxPackLayout::off_c2p; 64 / 128 fewer MFMAs per tile, 14 / 12 16-byte global loads per lane and tile instead of 8) and runs only the remaining taps; 0 = all taps.  Launches that cannot take the conv1-table form silently run without it.  Same bits
+    int64_t cnn_pool_table = FX_POOL_TABLE_DEFAULT; // K1, canonical seq_len = 8 members, launches that would take the 16-wave unrolled form with the rows resident: 1 = a launch group whose members' pooled-feature tables (fx_model::d_pooltab) are fresh runs only the dense head (k_score_cnn_mfma_pooled); stale tables are built first when the launch has more than 4^8 rows per member; 2 = ... whatever its size; 0 = off.  Same bits
     int64_t cnn_quad_tail = 1;  // K1, unrolled seq_len = 8 form: the (tiles mod 4) last tiles of a workgroup are walked by wave quads in one round behind the main loop; 0 = one wave per tile throughout (rounds 1-5)
     int64_t wave_prio = 1;      // 1 = static, distinct issue priorities for the waves of a SIMD (fx_stagger_priority); 0 = A/B baseline
     int64_t trace = 0;          // 1 = the MFMA scoring kernels stamp an in-kernel timeline into d_trace (fx_debug_trace_read)
@@ -441,6 +447,11 @@ struct fx_model {
     // GlobalEpistasis first layer as a per-position table indexed by the RAW byte (score_dense_mfma.hip): Lpad x 32
     // floats, tab[l][b - base] = w1[l * A + lut[b]] (0 for bytes outside the alphabet and for the padding rows l >= L);
     // built on the device for the LUT of the call, rebuilt when the weights or the LUT change
+    // Canonical seq_len = 8 CNN (FxPackLayout::off_c1tab >= 0): the global-max-pooled conv features of every possible row, 4^8 rows of 32 floats
+    // (row = sum_j code[j] * 4^j, channel 16 t + 4 g + r at float 16 t + 4 g + r), an allocation of its own made when a launch first asks for it
+    // (score_cnn_pooled.hip).  Fresh iff pooltab_version == version: fx_model_set_weights makes it stale without doing any work
+    float* d_pooltab = nullptr;
+    uint64_t pooltab_version = 0;
     float* d_bytetab = nullptr;
     uint8_t bt_lut[256];
     bool bt_valid = false;
@@ -547,6 +558,12 @@ int fx_build_conv1_table(fx_engine* e, fx_model* m);
 // conv2's prefix tables of such a member (FxPackLayout::off_c2p, every depth compiled in) from the conv1 table and the packed conv2 blocks in
 // m->d_packed: enqueued on e->stream right behind fx_build_conv1_table; a no-op for every other model
 int fx_build_conv2_prefix(fx_engine* e, fx_model* m);
+// the head-only form of a launch group of canonical seq_len = 8 members (score_cnn_pooled.hip): builds the stale members' tables first when
+// `build`; FX_EUNSUPPORTED (nothing enqueued for the scores) when a table could not be allocated: the caller launches its conv form
+int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
+                               bool build);
+// the conv part of the two-kernel path alone, one 4-letter member: tile-major pooled features into d_pool (score_cnn_split.hip; test hook)
+int fx_launch_cnn_conv_only(fx_engine* e, fx_model* model, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_cnn_pair_conv(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
                               int64_t N, float* d_out_NM, int Mtot, int m_off);

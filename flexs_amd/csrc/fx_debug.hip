@@ -132,6 +132,63 @@ int fx_debug_cnn_form_pick(int path, int L, int A, int F, int H, int K, int64_t 
     auto fields = [&](auto form) { fx_cnn_form_fields<decltype(form)>(out24); return (int)FX_OK; };
     return path == 0 ? fx_cnn_with_fused_form(pk, fields) : fx_cnn_with_conv_form(pk, fields);
 }
+// Host only: what a launch group of M such members on N rows does about the pooled-feature tables (fx_cnn_pool_decide on the pick of
+// fx_cnn_pick_fused, same engine and overrides as fx_debug_cnn_form_pick; `fresh`: every member's table is).  out4 = the CnnPoolDecision
+// (0 conv form, 1 head-only kernel, 2 build first), the pick's CnnFormId, 1 if the shape may carry a table, the pick's status.
+int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host, int fresh,
+                           const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out4) {
+    if (!out4 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
+    fx_engine eng;
+    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    std::memset(out4, 0, 4 * sizeof(int64_t));
+    for (int i = 0; i < n_opts; ++i) {
+        int64_t* slot = nullptr;
+        if (int rc = fx_option_slot_for(&eng, opt_keys[i], opt_values[i], &slot)) return rc;
+        *slot = opt_values[i];
+    }
+    const FxShape s{FX_CNN, L, A, F, H, K};
+    const FxPackLayout lay = fx_pack_layout(s);
+    out4[2] = lay.off_c1tab >= 0;
+    if (int rc = fx_cnn_fused_supported(&eng, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
+    const CnnPick pk = fx_cnn_pick_fused(&eng, s, lay, N, M);
+    out4[0] = fx_cnn_pool_decide(&eng, lay, pk, N, fresh != 0);
+    out4[1] = pk.id; out4[3] = pk.rc;
+    return FX_OK;
+}
+// Needs the GPU: the global-max-pooled conv features of N rows (host memory, N x L bytes) as the CONV-ONLY kernel of the two-kernel path leaves them,
+// row-major (N x 16 FT floats, channel 16 t + 4 g + r at float 16 t + 4 g + r): what the pooled-feature table is held to row by row.
+int fx_debug_cnn_conv_features(fx_model* m, const uint8_t* rows, int64_t N, const uint8_t lut[256], float* out, int64_t cap) {
+    if (!m || !rows || !lut || !out || N < 1) return FX_EINVAL;
+    fx_engine* e = m->eng;
+    if (m->shape.kind != FX_CNN) return FX_EUNSUPPORTED;
+    if (!m->has_weights) return fx_fail(e, FX_ESTATE, "model has no weights");
+    const int FT = m->layout.FT, L = m->shape.L;
+    const int64_t TG = (N + 15) / 16;
+    if (cap < N * 16 * FT) return FX_EINVAL;
+    FX_HIP(e, hipSetDevice(e->device));
+    if (int rc = fx_upload_lut(e, lut)) return rc;
+    uint8_t* d_rows = nullptr;
+    float* d_pool = nullptr;
+    std::vector<float> pool((size_t)TG * FT * 256);
+    FX_HIP(e, hipMalloc(&d_rows, (size_t)N * L + 16));
+    if (hipMalloc(&d_pool, pool.size() * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_rows); return FX_ENOMEM; }
+    int rc = FX_OK;
+    hipError_t he = hipMemcpyAsync(d_rows, rows, (size_t)N * L, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) {
+        rc = fx_launch_cnn_conv_only(e, m, d_rows, N, d_pool);
+        if (!rc) he = hipMemcpyAsync(pool.data(), d_pool, pool.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+    }
+    const hipError_t hs = hipStreamSynchronize(e->stream);
+    (void)hipFree(d_rows); (void)hipFree(d_pool);
+    if (rc) return rc;
+    if (he != hipSuccess || hs != hipSuccess) return fx_fail(e, FX_EHIP, hipGetErrorString(he != hipSuccess ? he : hs));
+    if ((rc = check_deferred(e))) return rc;
+    for (int64_t n = 0; n < N; ++n)
+        for (int t = 0; t < FT; ++t)
+            for (int g = 0; g < 4; ++g)
+                std::memcpy(out + (n * FT + t) * 16 + 4 * g, pool.data() + (((n >> 4) * FT + t) * 64 + (g * 16 + (n & 15))) * 4, 16);
+    return FX_OK;
+}
 int fx_debug_pack_weights(int kind, int L, int A, int F, int H, int K, const float* blob, int64_t n, float* packed,
                           int64_t cap) {
     const FxShape s{kind, L, A, F, H, K};

@@ -321,6 +321,7 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "ge_bytetab")) return &e->ge_bytetab;
     if (!std::strcmp(key, "wave_prio")) return &e->wave_prio;
     if (!std::strcmp(key, "cnn_quad_tail")) return &e->cnn_quad_tail;
+    if (!std::strcmp(key, "cnn_pool_table")) return &e->cnn_pool_table;
     if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
     if (!std::strcmp(key, "cnn_conv2_prefix")) return &e->cnn_conv2_prefix;
     if (!std::strcmp(key, "cnn_head_slab")) return &e->cnn_head_slab;
@@ -386,6 +387,8 @@ int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** s
     if (!s) return fx_fail(e, FX_EINVAL, std::string("unknown option ") + (key ? key : "(null)"));
     if (s == &e->cnn_conv2_prefix && (value < 0 || value > FX_C2P_MAX_DEPTH))
         return fx_fail(e, FX_EINVAL, "cnn_conv2_prefix is 0 (off) or a depth that is compiled in (1, 2)");
+    if (s == &e->cnn_pool_table && (value < 0 || value > 2))
+        return fx_fail(e, FX_EINVAL, "cnn_pool_table is 0 (off), 1 (build for launches of more than 4^8 rows) or 2 (build for any launch)");
     if (ab_only_value(e, s, value))
         return fx_fail(e, FX_EUNSUPPORTED, std::string("option ") + key + " = " + std::to_string(value) + " selects a kernel form of the A/B build "
                        "(measured slower, see csrc/OPTIONS.md): make -C flexs_amd/csrc ab, FLEXS_AMD_LIB=.../libflexs_amd_ab.so");
@@ -426,6 +429,8 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "launch_first_redone")) { *value = e->launch_first_redone; return FX_OK; }
     if (e && key && !std::strcmp(key, "conv1_table_launches")) { *value = e->counters.conv1_table_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "conv2_prefix_launches")) { *value = e->counters.conv2_prefix_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "pool_table_launches")) { *value = e->counters.pool_table_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "pool_table_builds")) { *value = e->counters.pool_table_builds; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "large_bar")) { *value = (e->large_bar && !e->rows_refused) ? 1 : 0; return FX_OK; }   // (the host can store into device memory: resident forms, launched-first calls)
     if (e && key && !std::strcmp(key, "server_streamed")) { *value = e->server.streamed; return FX_OK; }
@@ -509,6 +514,7 @@ int fx_model_destroy(fx_model* m) {
     if (m->d_blob) (void)hipFree(m->d_blob);
     if (m->d_packed) (void)hipFree(m->d_packed);
     if (m->d_bytetab) (void)hipFree(m->d_bytetab);
+    if (m->d_pooltab) (void)hipFree(m->d_pooltab);
     delete m;
     return FX_OK;
 }

@@ -19,6 +19,7 @@ struct CnnForm {
     static constexpr int L1S = 0;
     static constexpr bool PRIO = false, SEG = false, HEAD = true, STG = false, QT = false, C1T = false;
     static constexpr int C2P = 0;
+    static constexpr bool PTB = false;
 };
 // A form shadows what it changes.  (A kernel is instantiated per TYPE: the switches below are the only place that spells these, so that one
 // set of field values has one spelling.)
@@ -31,6 +32,7 @@ template <class F> struct HostStaged : F { static constexpr bool STG = true; };
 template <class F> struct QuadTail : F { static constexpr bool QT = true; };
 template <class F> struct Conv1Table : F { static constexpr bool C1T = true; };
 template <class F, int DEPTH> struct Conv2Prefix : Conv1Table<F> { static constexpr int C2P = DEPTH; };   // (no C2P without C1T)
+template <class F> struct PoolTableBuild : F { static constexpr bool PTB = true; };   // (a conv-only form: the rows are the tile indices, the features go to the member's table)
 template <class F> struct Conv1Mfma : F { static constexpr bool G1 = false; };
 template <class F> struct TwoTiles : F { static constexpr int NT = 2; };
 template <class F> struct HeadFromL2 : F { static constexpr bool DENSE_LDS = false; };
@@ -54,6 +56,7 @@ using CnnSeg8 = Segmented<CnnForm>;                          // the waves of a w
 using CnnSeg4 = Segmented<Waves4<CnnForm>>;                  // ... in 4-wave workgroups, several per tile
 template <int HT_> using CnnHidden8 = HiddenTiles<CnnForm, HT_>;                     // other hidden widths (HT_ tiles of 16 units)
 template <int K_, int FT_> using CnnConv = ConvOnly<FilterTiles<Kernel<CnnForm, K_>, FT_>>;   // the split path's conv-only forms (score_cnn_split.hip)
+using CnnPoolTableBuild = PoolTableBuild<Unrolled<Waves16<CnnConv<5, 2>>, 4>>;   // the builder of the pooled-feature table (score_cnn_pooled.hip): the unrolled conv-only walk over all 4^8 rows
 using CnnBinary8 = Alphabet<CnnForm, 2>;                     // binary alphabet
 using CnnNarrow8 = FilterTiles<CnnForm, 1>;                  // at most 16 filters
 using CnnNarrowProtein8 = Alphabet<CnnNarrow8, 20>;
@@ -331,6 +334,26 @@ int fx_cnn_with_fused_form(const CnnPick& pk, Fn&& fn) {
         case CNN_K7_W8: return fn(CnnK7W8{});
         default: return FX_EUNSUPPORTED;
     }
+}
+
+// ---------------------------------------------------------------- pooled-feature table (score_cnn_pooled.hip)
+// A seq_len = 8 row over four letters has 4^8 values, and everything in front of the dense head is a function of the row alone: a canonical
+// member (the shapes with a conv1 table, FxPackLayout::off_c1tab) may carry its global-max-pooled features for every row, FX_POOL_ROWS lines of 32
+// floats, and a launch then runs only the head (k_score_cnn_mfma_pooled).  What a launch group does about it (engine option cnn_pool_table):
+#define FX_POOL_ROWS 65536      // 4^8 rows, index = sum_j code[j] * 4^j: the 16-bit `codes` word of the C1T branch
+enum CnnPoolDecision : int {
+    CNN_POOL_NO = 0,            // the form fx_cnn_pick_fused named is launched, as without the option
+    CNN_POOL_USE = 1,           // every member's table is fresh: the head-only kernel
+    CNN_POOL_BUILD = 2,         // the stale members' tables are built first, then the head-only kernel
+};
+// `pk` is the launch's pick and is launched unchanged when the answer is CNN_POOL_NO.  The table form stands in for the 16-wave unrolled form
+// only, with the rows in device memory when the kernel starts.  A stale table is built when the launch is longer than the enumeration (MORE
+// than 4^8 rows per member: building is then no more conv work than the launch would do itself), or whatever its size with cnn_pool_table = 2.
+inline CnnPoolDecision fx_cnn_pool_decide(const fx_engine* e, const FxPackLayout& lay, const CnnPick& pk, int64_t N, bool all_fresh) {
+    if (e->cnn_pool_table <= 0 || lay.off_c1tab < 0) return CNN_POOL_NO;
+    if (pk.rc || pk.id != CNN_UNROLLED8_W16 || pk.stg || e->rows_req.on || e->ascii_host) return CNN_POOL_NO;
+    if (all_fresh) return CNN_POOL_USE;
+    return (e->cnn_pool_table >= 2 || N > FX_POOL_ROWS) ? CNN_POOL_BUILD : CNN_POOL_NO;
 }
 
 // ---------------------------------------------------------------- conv part of the two-kernel path (score_cnn_split.hip)

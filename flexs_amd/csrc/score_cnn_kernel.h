@@ -152,11 +152,18 @@ __device__ __forceinline__ void fx_fused_mean_tile(float* planes, int64_t stride
 // the conv1 table's rows: the same bits).  A tile loads its four positions' prefixes (eight 16-byte pieces) into what becomes o2, runs only the
 // remaining taps -- 64 / 128 MFMAs fewer per tile -- and no longer asks for the first C2P conv1 rows, which nothing reads any more: 14 / 12
 // loads per lane and tile, issued in the order of first use.  The quad round keeps the gather and all taps.
+//
+// PTB (a conv-only form, HEAD = false; score_cnn_pooled.hip): the builder of a member's pooled-feature table.  The "batch" is the enumeration of all
+// 4^8 rows: the letter codes of lane sq of tile tg are the bits of 16 tg + sq (two per letter, letter j at bits 2j) where every other form reads
+// lut_s[byte j of the row] -- no row, no LUT -- and the pooled features leave row-major, 32 floats per row with channel 16 t + 4 g + r at float
+// 16 t + 4 g + r, into the table `pool_out` points at (one member per launch).  Everything between is this kernel's own walk: the same bits.
 template <class Form>
 __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) {
     constexpr int A = Form::A, K = Form::K, FT = Form::FT, HT = Form::HT, NT = Form::NT, WAVES = Form::WAVES, L1S = Form::L1S, C2P = Form::C2P;
     constexpr bool DENSE_LDS = Form::DENSE_LDS, G1 = Form::G1, PRIO = Form::PRIO, SEG = Form::SEG, HEAD = Form::HEAD, STG = Form::STG, QT = Form::QT,
-                   C1T = Form::C1T;
+                   C1T = Form::C1T, PTB = Form::PTB;
+    static_assert(!PTB || (!HEAD && !C1T && !SEG && !STG && NT == 1 && A == 4 && K == 5 && FT == 2 && L1S == 4 && G1),
+                  "PTB enumerates the 4^8 rows of a seq_len = 8 member: a conv-only form of the unrolled walk");
     static_assert(C2P >= 0 && C2P <= FX_C2P_MAX_DEPTH && (C2P == 0 || C1T), "C2P is a form of C1T: its index is cut from C1T's codes and the remaining taps read C1T's rows");
     static_assert(!C1T || (A == 4 && K == 5 && FT == 2 && HT == 7 && NT == 1 && DENSE_LDS && WAVES == 16 && G1 && L1S == 4 && !SEG && HEAD && !STG),
                   "C1T reads the table of 4^5 windows x 32 channels; the four positions of a seq_len = 8 row; built and measured in 16-wave workgroups");
@@ -324,8 +331,13 @@ __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) 
             [[maybe_unused]] unsigned long long rowq[NT];
             if constexpr (ROW8) {
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) __builtin_memcpy(&rowq[nt], row[nt], 8);
+                for (int nt = 0; nt < NT; ++nt) {
+                    if constexpr (PTB) rowq[nt] = 0;       // (never read: ptb_code below)
+                    else __builtin_memcpy(&rowq[nt], row[nt], 8);
+                }
             }
+            [[maybe_unused]] const unsigned ptb_codes = (unsigned)(tg * 16 + sq);   // PTB: the row's eight codes
+            auto ptb_code = [&](int at) -> int { return (int)((ptb_codes >> (2 * at)) & 3u); };
             auto seq_byte = [&](int nt, int at) -> int {
                 if constexpr (STG) return (int)srow[at];
                 else if constexpr (ROW8) return (int)((rowq[nt] >> (8 * at)) & 0xFFull);
@@ -376,7 +388,7 @@ __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) 
             for (int j = 0; j < K - 1; ++j)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    int c = lut_s[seq_byte(nt, j)];
+                    int c = PTB ? ptb_code(j) : (int)lut_s[seq_byte(nt, j)];
                     if (c == 0xFF) { bad = true; c = 0; }
                     cw[RING ? j : j + 1][nt] = c;         // (shifting form: moved down at the top of step 0)
                 }
@@ -489,7 +501,7 @@ __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) 
                             }
                             if (s + K - 1 + PF < L) rq[RING ? slot : PF - 1][nt] = seq_byte(nt, s + K - 1 + PF);
                         }
-                        int c = lut_s[raw];
+                        int c = PTB ? ptb_code(s + K - 1) : (int)lut_s[raw];
                         if (c == 0xFF) { bad = true; c = 0; }
                         cw[FX_CW(K - 1)][nt] = c;
                     }
@@ -639,7 +651,12 @@ __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) 
                     }
                 }
             }
-            if constexpr (!HEAD) {
+            if constexpr (PTB) {
+                float* dst = reinterpret_cast<float*>(p.pool_out) + (tg * 16 + sq) * (16 * FT) + 4 * g;
+#pragma unroll
+                for (int t = 0; t < FT; ++t) *reinterpret_cast<f4*>(dst + 16 * t) = gmax[t][0];
+                continue;
+            } else if constexpr (!HEAD) {
                 f4* dst = p.pool_out + (((int64_t)m * p.TG + tg) * FT) * 64 + lane;
 #pragma unroll
                 for (int t = 0; t < FT; ++t) dst[t * 64] = gmax[t][0];

@@ -49,6 +49,21 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
         if (rc != FX_EUNSUPPORTED) return rc;
     }
     if (pk.rc) return pk.msg ? fx_fail(e, pk.rc, pk.msg) : pk.rc;
+    {
+        // canonical seq_len = 8 members whose pooled-feature tables are fresh (or are built now): only the head runs (score_cnn_pooled.hip).  The
+        // in-kernel timeline and the fused mean of the A/B build belong to the conv forms
+        bool fresh = true;
+        for (int m = 0; m < M; ++m) fresh = fresh && models[m]->d_pooltab && models[m]->pooltab_version == models[m]->version;
+        CnnPoolDecision pool = fx_cnn_pool_decide(e, lay, pk, N, fresh);
+        if (a.trace) pool = CNN_POOL_NO;
+#if defined(FX_AB)
+        if (a.fm_mean) pool = CNN_POOL_NO;
+#endif
+        if (pool != CNN_POOL_NO) {
+            const int rc = fx_launch_score_cnn_pooled(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, pool == CNN_POOL_BUILD);
+            if (rc != FX_EUNSUPPORTED) return rc;       // (no table could be had: the form picked above)
+        }
+    }
     a.TG = pk.TG;
     a.quad_tail = pk.qt ? 1 : 0;
     a.seg_sb = pk.seg_sb;

@@ -242,3 +242,24 @@ int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, cons
     return by_channel_tiles<HeadArgs>(lay.FT, [&] { return dispatch_head<1>(e, h, lay.HT); }, [&] { return dispatch_head<2>(e, h, lay.HT); },
                                       [&] { return dispatch_head<3>(e, h, lay.HT); }, [&] { return dispatch_head<4>(e, h, lay.HT); });
 }
+
+// The conv part alone, one 4-letter member (fx_debug_cnn_conv_features): the pooled features of every tile, tile-major as the head kernel reads them
+// ([tile * FT + t][64 lanes] f4), into d_pool.  The form is the one the two-kernel path would launch for this shape and size.
+int fx_launch_cnn_conv_only(fx_engine* e, fx_model* model, const uint8_t* d_ascii, int64_t N, void* d_pool) {
+    const FxShape& s = model->shape;
+    const FxPackLayout& lay = model->layout;
+    if (s.kind != FX_CNN || s.A == 20 || N < 1) return FX_EUNSUPPORTED;
+    if (int rc = fx_cnn_split_supported(e, s, lay, 1)) return rc;
+    CnnArgs a{};
+    a.ascii = d_ascii; a.lut = e->d_lut; a.err = e->d_err;
+    a.w[0] = model->d_packed;
+    a.out_sn = 1; a.out_sm = 1;
+    a.N = N; a.TG = (N + 15) / 16; a.M = 1; a.Mtot = 1; a.L = s.L; a.rlh = 4;
+    a.off_first = (int)lay.off_first; a.off_c2 = (int)lay.off_c2; a.off_c3 = (int)lay.off_c3;
+    a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
+    a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
+    a.pool_out = (f4*)d_pool;
+    const CnnPick pk = fx_cnn_pick_conv(e, s, lay, N, 1);
+    if (pk.rc) return pk.rc;
+    return fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, a, pk.lds); });
+}

@@ -468,6 +468,20 @@ int64_t fx_debug_conv1_table(fx_model *m, float *out, int64_t cap);
  * fx_model_set_weights.  Returns the number of floats copied (cap must hold 98304 / 393216), FX_EUNSUPPORTED for shapes without
  * tables, FX_EINVAL for any other depth. */
 int64_t fx_debug_conv2_prefix(fx_model *m, int depth, float *out, int64_t cap);
+/* Needs the GPU: the pooled-feature table of a 4-letter seq_len = 8 CNN (what the dense head starts from, for every one of the 4^8
+ * rows: 65536 rows of 32 floats, row = sum_j code[j] * 4^j, channel order as packed) as the device built it.  Returns the number
+ * of floats copied (cap must hold 2097152), FX_EUNSUPPORTED for shapes without a table, FX_ESTATE when none has been built for
+ * the model's current weights (engine option cnn_pool_table). */
+int64_t fx_debug_pool_table(fx_model *m, float *out, int64_t cap);
+/* Needs the GPU: the pooled conv features of N rows (host memory, N x seq_len bytes) as the conv-only kernel of the two-kernel CNN
+ * path leaves them, row-major: N x 16 * ceil(F / 16) floats. */
+int fx_debug_cnn_conv_features(fx_model *m, const uint8_t *rows, int64_t N, const uint8_t lut[256], float *out, int64_t cap);
+/* Host only: what a launch group of M members of CNN(F, H, K) on N rows does about the pooled-feature tables under the engine
+ * option cnn_pool_table (arguments as fx_debug_cnn_form_pick; fresh: every member's table is).  out4 = {0 the picked conv form is
+ * launched / 1 the head-only kernel / 2 the stale tables are built first, the pick's form id, 1 if the shape may carry a table,
+ * the pick's status}. */
+int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host,
+                           int fresh, const char *const *opt_keys, const int64_t *opt_values, int n_opts, int64_t *out4);
 /* Host only: {alloc_floats, dev_floats, off_c1tab, c1tab_floats, off_c2p[0], c2p_floats[0], off_c2p[1], c2p_floats[1]} of the
  * device buffer of a model of this shape (floats; offsets -1 and sizes 0 where the shape carries no table), and the row of a
  * depth's prefix tables that conv position p (0..3) of a seq_len = 8 row reads (codes: two bits per letter, letter i at bits 2i). */
