@@ -549,6 +549,61 @@ class Engine:
         arr = (_vp * len(models))(*[m.handle for m in models])
         self.check(self._lib.fx_score_mean_planes_dev(self.handle, arr, len(models), _vp(d_ascii), N, L, _lut_ptr(lut), _vp(d_planes), stride, _vp(d_out32)))
 
+    # ---- screening: score + top-k select on the device (ordering rule: include/flexs_amd.h "screening")
+    def topk_dev(self, d_scores: int, N: int, k: int, d_idx: int, d_val: int) -> int:
+        """The min(k, N) best of N float32 scores at device address `d_scores`, best first, into `d_idx` (int64) / `d_val`
+        (float32), in stream order.  Returns the count."""
+        n = C.c_int(0)
+        self.check(self._lib.fx_topk_dev(self.handle, _vp(d_scores) if d_scores else None, N, k, _vp(d_idx) if d_idx else None,
+                                         _vp(d_val) if d_val else None, C.byref(n)))
+        return n.value
+
+    def topk(self, scores: np.ndarray, k: int):
+        """`topk_dev` for a host array: (idx int64, val float32)."""
+        s = np.ascontiguousarray(scores, np.float32).reshape(-1)
+        idx = np.full(min(max(k, 0), 4096, s.shape[0]), -1, np.int64)
+        val = np.full(idx.shape[0], np.nan, np.float32)
+        n = C.c_int(0)
+        self.check(self._lib.fx_topk(self.handle, _ptr(s), s.shape[0], k, _ptr(idx), _ptr(val), C.byref(n)))
+        return idx[:n.value], val[:n.value]
+
+    def score_topk(self, models: Sequence["NativeModel"], seq_bytes: np.ndarray, lut: np.ndarray, k: int):
+        """Scores (N, L) rows with `models` (one member: its score; several: their NumPy-order mean) and returns the k best
+        (row number, score) pairs; the score vector never leaves the device."""
+        N, L = seq_bytes.shape
+        M = len(models)
+        arr = (_vp * M)(*[m.handle for m in models])
+        seq_bytes = np.ascontiguousarray(seq_bytes)
+        idx = np.full(min(max(k, 0), 4096, N), -1, np.int64)
+        val = np.full(idx.shape[0], np.nan, np.float32)
+        n = C.c_int(0)
+        self.check(self._lib.fx_score_topk(self.handle, arr, M, _ptr(seq_bytes), N, L, _lut_ptr(lut), k, _ptr(idx), _ptr(val), C.byref(n)))
+        return idx[:n.value], val[:n.value]
+
+    def score_topk_dev(self, models: Sequence["NativeModel"], d_ascii: int, N: int, L: int, lut: np.ndarray, k: int,
+                       d_idx: int, d_val: int) -> int:
+        M = len(models)
+        arr = (_vp * M)(*[m.handle for m in models])
+        n = C.c_int(0)
+        self.check(self._lib.fx_score_topk_dev(self.handle, arr, M, _vp(d_ascii) if d_ascii else None, N, L, _lut_ptr(lut), k,
+                                               _vp(d_idx) if d_idx else None, _vp(d_val) if d_val else None, C.byref(n)))
+        return n.value
+
+    def screen_all(self, models: Sequence["NativeModel"], L: int, alphabet: str, lut: np.ndarray, k: int):
+        """The k best of ALL len(alphabet) ** L sequences, enumerated on the device in itertools.product order:
+        (row numbers int64, (count, L) uint8 rows, scores float32)."""
+        M = len(models)
+        arr = (_vp * M)(*[m.handle for m in models])
+        al = np.frombuffer(alphabet.encode("latin-1"), np.uint8).copy()
+        cap = min(max(k, 0), 4096)
+        idx = np.full(cap, -1, np.int64)
+        rows = np.zeros((cap, L), np.uint8)
+        val = np.full(cap, np.nan, np.float32)
+        n = C.c_int(0)
+        self.check(self._lib.fx_screen_all(self.handle, arr, M, L, al.shape[0], _ptr(al), _lut_ptr(lut), k, _ptr(idx), _ptr(rows),
+                                           _ptr(val), C.byref(n)))
+        return idx[:n.value], rows[:n.value], val[:n.value]
+
     def encode_onehot(self, seq_bytes: np.ndarray, lut: np.ndarray, A: int) -> np.ndarray:
         N, L = seq_bytes.shape
         out = np.empty((N, L, A), np.float32)

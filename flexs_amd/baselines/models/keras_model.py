@@ -145,6 +145,18 @@ class KerasModel(flexs_amd.Model):
         training.fit(self.model, sequences, labels, self.alphabet, batch_size=self.batch_size,
                      epochs=self.epochs, verbose=verbose, seed=seed)
 
+    def screen(self, sequences: SEQUENCES_TYPE, k: int):
+        """The k best of `sequences`: (positions, scores), best first, selected on the device (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen(self, sequences, k)
+
+    def screen_all(self, k: int):
+        """The k best of ALL len(alphabet) ** seq_len sequences: (sequences, scores) (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen_all(self, k)
+
     def _fitness_function(self, sequences):
         """keras_model.py:69-79: encode -> float32 tensor -> predict -> squeeze ->
         nan_to_num, fused on the GPU.  Returns float32 (N,)."""

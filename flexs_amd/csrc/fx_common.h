@@ -214,6 +214,7 @@ struct fx_engine {
         int64_t conv1_table_launches = 0;   // K1 launches that took the conv1-table form (read: option "conv1_table_launches")
         int64_t pool_table_launches = 0;    // launch groups answered by the head-only kernel from the members' pooled-feature tables (read: option "pool_table_launches")
         int64_t pool_table_builds = 0;      // pooled-feature tables built, one per member and build (read: option "pool_table_builds")
+        int64_t topk_large_launches = 0;    // selects answered by the radix-select form (read: option "topk_large_launches")
         int64_t conv2_prefix_launches = 0;  // ... and, of those, the ones that read conv2's first taps from the prefix tables (read: option "conv2_prefix_launches")
     } counters;
     // deferred error word (device) + pinned host mirror
@@ -225,8 +226,8 @@ struct fx_engine {
     uint8_t h_lut[256];
     bool lut_valid = false;
     // growable scratch
-    void* d_scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // (5: the relay area of a plain host call, FxRelay)
-    size_t scratch_bytes[6] = {0, 0, 0, 0, 0, 0};
+    void* d_scratch[10] = {};   // (5: the relay area of a plain host call, FxRelay; 6 - 9: top-k select and screening, fx_screen.hip)
+    size_t scratch_bytes[10] = {};
     void* d_train = nullptr;      // fx_train_fit arena (grown on demand, kept between fits)
     size_t train_bytes = 0;
     int64_t train_prof_ns[5] = {};   // the last fx_train_fit: ns since entry at "image filled", "upload enqueued", "launches enqueued", "synchronised", "results copied out"
@@ -259,6 +260,8 @@ struct fx_engine {
     int64_t cnn_conv1_table = 1; // K1, unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts: 1 = conv1's four outputs of a tile are READ from the member's table of all 4^5 windows (FxPackLayout::off_c1tab; eight 16-byte global loads per lane and tile) instead of gathered from LDS and summed; 0 = the gather (rounds 1-6: A/B).  Same bits
     int64_t cnn_conv2_prefix = FX_C2P_DEFAULT; // K1, the conv1-table form (cnn_conv1_table = 1, rows resident, a member with tables): 1 / 2 = a tile READS conv2's accumulator after the first one / two valid taps of each of its four positions from the member's prefix tables (FxPackLayout::off_c2p; 64 / 128 fewer MFMAs per tile, 14 / 12 16-byte global loads per lane and tile instead of 8) and runs only the remaining taps; 0 = all taps.  Launches that cannot take the conv1-table form silently run without it.  Same bits
     int64_t cnn_pool_table = FX_POOL_TABLE_DEFAULT; // K1, canonical seq_len = 8 members, launches that would take the 16-wave unrolled form with the rows resident: 1 = a launch group whose members' pooled-feature tables (fx_model::d_pooltab) are fresh runs only the dense head (k_score_cnn_mfma_pooled); stale tables are built first when the launch has more than 4^8 rows per member; 2 = ... whatever its size; 0 = off.  Same bits
+    int64_t topk_small_rows = 4096;    // K8: selects over at most this many scores are sorted by ONE workgroup in LDS (0 .. 8192); larger ones run the radix select (topk.hip).  4096: up to there the sort (47 us at 4096 keys, 25 at 2048) is no slower than the ten launches of the select (44 us at k = 100, 73 at k = 4096); at 8192 keys it costs 93 us against 43 - 74, profiles/screen_topk.log
+    int64_t screen_chunk_rows = 1 << 22;   // fx_screen_all: rows enumerated, scored and selected per step (a multiple of 16)
     int64_t cnn_quad_tail = 1;  // K1, unrolled seq_len = 8 form: the (tiles mod 4) last tiles of a workgroup are walked by wave quads in one round behind the main loop; 0 = one wave per tile throughout (rounds 1-5)
     int64_t wave_prio = 1;      // 1 = static, distinct issue priorities for the waves of a SIMD (fx_stagger_priority); 0 = A/B baseline
     int64_t trace = 0;          // 1 = the MFMA scoring kernels stamp an in-kernel timeline into d_trace (fx_debug_trace_read)
@@ -694,5 +697,11 @@ int fx_launch_nam_table_blend(fx_engine* e, int64_t Q, const uint8_t* d_queries,
                               const double* d_alpha, int n_tab, double* d_out, int32_t* d_flags);
 int fx_launch_table_lookup(fx_engine* e, const double* d_table, int64_t len, const uint8_t* d_ascii, int64_t N,
                            int L, int bits, double* d_out);
+// K8 (topk.hip): the kk <= min(N, 4096) best of N scores, best first (ordering rule: include/flexs_amd.h, fx_topk_dev), as
+// (idx_base + index, value) pairs; the same over n <= 8192 candidates that carry their own (global) indices; rows row0 .. row0 + n
+// of the enumeration of all A^L sequences as N x L bytes
+int fx_launch_topk(fx_engine* e, const float* d_scores, int64_t N, int kk, int64_t idx_base, int64_t* d_idx, float* d_val);
+int fx_launch_topk_merge(fx_engine* e, const int64_t* d_gidx, const float* d_vals, int n, int kk, int64_t* d_idx, float* d_val);
+int fx_launch_enumerate_rows(fx_engine* e, uint8_t* d_rows, int64_t row0, int64_t n, int L, int A, const uint8_t* alphabet);
 int fx_launch_min_dist_finish(fx_engine* e, const unsigned long long* d_keys, int64_t Q, int64_t C,
                               int32_t* d_dist, int64_t* d_arg);

@@ -321,6 +321,8 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "ge_bytetab")) return &e->ge_bytetab;
     if (!std::strcmp(key, "wave_prio")) return &e->wave_prio;
     if (!std::strcmp(key, "cnn_quad_tail")) return &e->cnn_quad_tail;
+    if (!std::strcmp(key, "topk_small_rows")) return &e->topk_small_rows;
+    if (!std::strcmp(key, "screen_chunk_rows")) return &e->screen_chunk_rows;
     if (!std::strcmp(key, "cnn_pool_table")) return &e->cnn_pool_table;
     if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
     if (!std::strcmp(key, "cnn_conv2_prefix")) return &e->cnn_conv2_prefix;
@@ -389,6 +391,10 @@ int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** s
         return fx_fail(e, FX_EINVAL, "cnn_conv2_prefix is 0 (off) or a depth that is compiled in (1, 2)");
     if (s == &e->cnn_pool_table && (value < 0 || value > 2))
         return fx_fail(e, FX_EINVAL, "cnn_pool_table is 0 (off), 1 (build for launches of more than 4^8 rows) or 2 (build for any launch)");
+    if (s == &e->topk_small_rows && (value < 0 || value > 8192))
+        return fx_fail(e, FX_EINVAL, "topk_small_rows is 0 .. 8192 (what one workgroup sorts in LDS)");
+    if (s == &e->screen_chunk_rows && (value < 16 || value > (1 << 26) || (value & 15)))
+        return fx_fail(e, FX_EINVAL, "screen_chunk_rows is a multiple of 16 between 16 and 2^26");
     if (ab_only_value(e, s, value))
         return fx_fail(e, FX_EUNSUPPORTED, std::string("option ") + key + " = " + std::to_string(value) + " selects a kernel form of the A/B build "
                        "(measured slower, see csrc/OPTIONS.md): make -C flexs_amd/csrc ab, FLEXS_AMD_LIB=.../libflexs_amd_ab.so");
@@ -430,6 +436,7 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "conv1_table_launches")) { *value = e->counters.conv1_table_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "conv2_prefix_launches")) { *value = e->counters.conv2_prefix_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "pool_table_launches")) { *value = e->counters.pool_table_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "topk_large_launches")) { *value = e->counters.topk_large_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "pool_table_builds")) { *value = e->counters.pool_table_builds; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "large_bar")) { *value = (e->large_bar && !e->rows_refused) ? 1 : 0; return FX_OK; }   // (the host can store into device memory: resident forms, launched-first calls)

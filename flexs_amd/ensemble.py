@@ -79,6 +79,19 @@ class Ensemble(_EnsembleBase):
         seeds = None if seed is None else [seed + k for k in range(len(self.models))]
         train_members(self.models, sequences, labels, seeds)
 
+    def screen(self, sequences: SEQUENCES_TYPE, k: int):
+        """The k best of `sequences` under the ensemble: (positions, scores), best first; on the device when every member is
+        a device surrogate and `combine_with` is the default mean (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen(self, sequences, k)
+
+    def screen_all(self, k: int):
+        """The k best of the members' whole sequence space: (sequences, scores) (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen_all(self, k)
+
     _small = None                                          # explorer-size fast path: (members, fx_models, {want_mean: plan})
 
     def __getstate__(self):

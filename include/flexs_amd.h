@@ -168,6 +168,10 @@ const char *fx_last_error(fx_engine *e);
  *   cnn_lp            1        1 = small batches of the canonical protein CNN run layer-parallel over the chip (conv2
  *                              outputs through device memory, one grid barrier) instead of position segments with
  *                              recomputed halos: a 237-residue call 64 -> 24 us, same bits.  0 = the segmented form.
+ *   topk_small_rows   4096     fx_topk* / fx_score_topk* / fx_screen_all: selects over at most this many scores (0 .. 8192) are
+ *                              sorted by one workgroup in LDS; larger ones run the radix select (one launch per pass).  Same
+ *                              answer either way.  topk_large_launches (read): selects answered by the radix select.
+ *   screen_chunk_rows 4194304  fx_screen_all: rows enumerated, scored and selected per step (a multiple of 16, <= 2^26).
  *   train_canon       1        fx_train_fit: canonical shapes run the step instantiated with compile-time dimensions
  *                              (k_train_fb 47.8 -> 29.8 us with the padded LDS rows, same bits); 0 = the shape-agnostic
  *                              code for everything.
@@ -313,6 +317,32 @@ int fx_ensemble_mean_planes_dev(fx_engine *e, const float *d_planes, int64_t N, 
 int fx_score_mean_planes_dev(fx_engine *e, fx_model *const *models, int M, const uint8_t *d_ascii, int64_t N,
                              int L, const uint8_t lut[256], float *d_planes, int64_t stride, float *d_out_mean);
 
+/* ---------------------------------------------------------------- screening
+ * What every consumer of `get_fitness` does next -- `np.argsort(preds)[: -batch : -1]` (adalead.py:173, cmaes.py:120,
+ * cbas_dbas.py:199, random.py:84, genetic_algorithm.py:151): keep the best few -- on the device, so that only the k winners
+ * cross PCIe.  ORDERING RULE of everything below: the min(k, N) best entries, best first.  Value order is NumPy's sort order
+ * read from the top: NaN ranks above +inf, -0.0 and +0.0 are equal, denormals keep their own rank.  Among equal values the
+ * lower index wins and comes first.  The result depends on the input only (the same on every run).  1 <= k <= 4096, else
+ * FX_ESHAPE; N = 0 gives *out_count = 0; N >= 2^31 gives FX_ESHAPE.  *out_count = min(k, N) is set on return, also by the _dev
+ * forms (whose d_idx / d_val are written in stream order).  Values are returned with the bits they have in the input.
+ * Engine options: topk_small_rows (selects over at most that many scores are sorted by one workgroup, larger ones run a radix
+ * select, one launch per pass; read-only companion topk_large_launches), screen_chunk_rows (fx_screen_all).
+ * No allocation per call after the first call of a size. */
+int fx_topk_dev(fx_engine *e, const float *d_scores, int64_t N, int k, int64_t *d_idx, float *d_val, int *out_count);
+int fx_topk(fx_engine *e, const float *scores, int64_t N, int k, int64_t *idx, float *val, int *out_count);
+/* fx_score + the select in one call: ranks the member's score (M = 1) or the NumPy-order ensemble mean (M > 1) of N rows and
+ * returns the k best (row number, score); the score vector stays on the device.  The values are the bits fx_score returns for
+ * those rows.  A character outside the alphabet: FX_EBADCHAR and nothing written (the _dev form: at fx_engine_sync). */
+int fx_score_topk(fx_engine *e, fx_model *const *models, int M, const uint8_t *ascii, int64_t N, int L,
+                  const uint8_t lut[256], int k, int64_t *idx, float *val, int *out_count);
+int fx_score_topk_dev(fx_engine *e, fx_model *const *models, int M, const uint8_t *d_ascii, int64_t N, int L,
+                      const uint8_t lut[256], int k, int64_t *d_idx, float *d_val, int *out_count);
+/* The model's optimum set: all A^L sequences are enumerated ON THE DEVICE, chunk by chunk (engine option screen_chunk_rows),
+ * scored, and the best k kept.  Row i is the base-A digits of i, position 0 most significant, digit d -> alphabet[d]: the order
+ * of itertools.product(alphabet, repeat = L).  idx = the winners' row numbers, rows_kxL their k x L bytes, val their scores; ties
+ * go to the lower row number across chunks as within one.  A = the models' alphabet size; A^L > 2^31 - 1: FX_ESHAPE. */
+int fx_screen_all(fx_engine *e, fx_model *const *models, int M, int L, int A, const uint8_t *alphabet,
+                  const uint8_t lut[256], int k, int64_t *idx, uint8_t *rows_kxL, float *val, int *out_count);
 
 /* string_to_one_hot over a batch (sequence_utils.py:32-47 + keras_model.py:70-75):
  * N x L bytes -> N x L x A float32 0/1.  Stand-alone, HBM-bound. */
