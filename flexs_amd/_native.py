@@ -734,6 +734,16 @@ class NativeModel:
         assert n == out.size
         return out
 
+    def debug_score_table(self) -> np.ndarray:
+        """(65536,) scores per seq_len = 8 row (row = sum_j code[j] * 4^j) as the device built them for the current weights
+        (fx_debug_score_table; test hook; FxError while no fresh table exists)."""
+        out = np.empty(4 ** 8, np.float32)
+        n = self.engine._lib.fx_debug_score_table(self.handle, out.ctypes.data_as(_f32p), out.size)
+        if n < 0:
+            _raise(int(n), self.engine.handle)
+        assert n == out.size
+        return out
+
     def debug_conv_features(self, rows: np.ndarray, lut: np.ndarray) -> np.ndarray:
         """(N, 16 * filter tiles) pooled conv features of the (N, L) uint8 rows as the conv-only kernel of the two-kernel CNN path leaves
         them (fx_debug_cnn_conv_features; test hook)."""
@@ -939,6 +949,22 @@ def debug_cnn_pool_pick(L, A, F, H, K, N, M, *, fresh, num_cus=256, max_lds=160 
     if rc != FX_OK:
         raise ValueError(status_name(rc))
     return {"decision": POOL_DECISIONS[v[0]], "id": int(v[1]), "canonical": bool(v[2]), "rc": status_name(int(v[3]))}
+
+
+def debug_cnn_score_pick(L, A, F, H, K, N, M, *, fresh, num_cus=256, max_lds=160 * 1024, rows_on=False, ascii_host=False, options=None) -> dict:
+    """What a launch group does about the members' score tables on top of debug_cnn_pool_pick's answer (engine option cnn_score_table; host
+    only).  Keys: form ("conv": the picked conv form, "head": the head-only kernel, "lookup": the lookup kernel), build (stale tables are
+    built first), decision (debug_cnn_pool_pick's), id, rc."""
+    options = dict(options or {})
+    keys = (C.c_char_p * max(len(options), 1))(*[k.encode() for k in options])
+    vals = (C.c_int64 * max(len(options), 1))(*options.values())
+    v = (C.c_int64 * 4)()
+    rc = lib().fx_debug_cnn_score_pick(L, A, F, H, K, N, M, num_cus, max_lds, int(rows_on), int(ascii_host), int(fresh), keys, vals,
+                                       len(options), v)
+    if rc != FX_OK:
+        raise ValueError(status_name(rc))
+    form = "lookup" if v[0] else ("conv" if v[1] == 0 else "head")
+    return {"form": form, "build": v[1] == 2, "decision": POOL_DECISIONS[v[1]], "id": int(v[2]), "rc": status_name(int(v[3]))}
 
 
 def debug_table_layout(kind, L, A, F, H, K) -> dict:

@@ -119,6 +119,9 @@ struct FxPackLayout {
 #ifndef FX_POOL_TABLE_DEFAULT
 #define FX_POOL_TABLE_DEFAULT 1 // engine option cnn_pool_table as shipped (profiles/pool_table_ab.log; -DFX_POOL_TABLE_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
 #endif
+#ifndef FX_SCORE_TABLE_DEFAULT
+#define FX_SCORE_TABLE_DEFAULT 1 // engine option cnn_score_table as shipped (profiles/score_table_ab.log; -DFX_SCORE_TABLE_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
+#endif
 #define FX_C2P_FAMILIES 3       // first valid taps j0 = 0, 1, 2 of the four conv positions of a seq_len = 8 row
 #define FX_C2P_ENTRIES(depth) (1 << (2 * (4 + (depth))))   // 4^5 rows per family at depth 1, 4^6 at depth 2
 // conv2 ('same', five taps, tap j reads out1[p + j - 2]) at position p of the four conv positions: its first valid tap, the window that tap reads
@@ -212,8 +215,10 @@ struct fx_engine {
         int64_t pair_evals = 0;        // (query, cache entry) distance evaluations
         int64_t train_steps = 0;       // mini-batch steps x members run by fx_train_fit
         int64_t conv1_table_launches = 0;   // K1 launches that took the conv1-table form (read: option "conv1_table_launches")
-        int64_t pool_table_launches = 0;    // launch groups answered by the head-only kernel from the members' pooled-feature tables (read: option "pool_table_launches")
+        int64_t pool_table_launches = 0;    // launch groups answered from the members' tables, by the head-only kernel or by the lookup kernel (read: option "pool_table_launches")
         int64_t pool_table_builds = 0;      // pooled-feature tables built, one per member and build (read: option "pool_table_builds")
+        int64_t score_table_launches = 0;   // ... and, of those launch groups, the ones answered by the lookup kernel from the members' score tables (read: option "score_table_launches")
+        int64_t score_table_builds = 0;     // score tables built, one per member and build (read: option "score_table_builds")
         int64_t topk_large_launches = 0;    // selects answered by the radix-select form (read: option "topk_large_launches")
         int64_t conv2_prefix_launches = 0;  // ... and, of those, the ones that read conv2's first taps from the prefix tables (read: option "conv2_prefix_launches")
     } counters;
@@ -260,6 +265,7 @@ struct fx_engine {
     int64_t cnn_conv1_table = 1; // K1, unrolled seq_len = 8 form in 16-wave workgroups, rows resident when the kernel starts: 1 = conv1's four outputs of a tile are READ from the member's table of all 4^5 windows (FxPackLayout::off_c1tab; eight 16-byte global loads per lane and tile) instead of gathered from LDS and summed; 0 = the gather (rounds 1-6: A/B).  Same bits
     int64_t cnn_conv2_prefix = FX_C2P_DEFAULT; // K1, the conv1-table form (cnn_conv1_table = 1, rows resident, a member with tables): 1 / 2 = a tile READS conv2's accumulator after the first one / two valid taps of each of its four positions from the member's prefix tables (FxPackLayout::off_c2p; 64 / 128 fewer MFMAs per tile, 14 / 12 16-byte global loads per lane and tile instead of 8) and runs only the remaining taps; 0 = all taps.  Launches that cannot take the conv1-table form silently run without it.  Same bits
     int64_t cnn_pool_table = FX_POOL_TABLE_DEFAULT; // K1, canonical seq_len = 8 members, launches that would take the 16-wave unrolled form with the rows resident: 1 = a launch group whose members' pooled-feature tables (fx_model::d_pooltab) are fresh runs only the dense head (k_score_cnn_mfma_pooled); stale tables are built first when the launch has more than 4^8 rows per member; 2 = ... whatever its size; 0 = off.  Same bits
+    int64_t cnn_score_table = FX_SCORE_TABLE_DEFAULT; // K1, the launch groups that cnn_pool_table answers from the members' tables: 1 = from the members' tables of SCORES (fx_model::d_scoretab, built by the head-only kernel over all 4^8 rows when the pooled-feature table is built or found fresh): one 4-byte read per row and member (k_score_cnn_mfma_scoretab); 0 = the head-only kernel scores.  Same bits
     int64_t topk_small_rows = 4096;    // K8: selects over at most this many scores are sorted by ONE workgroup in LDS (0 .. 8192); larger ones run the radix select (topk.hip).  4096: up to there the sort (47 us at 4096 keys, 25 at 2048) is no slower than the ten launches of the select (44 us at k = 100, 73 at k = 4096); at 8192 keys it costs 93 us against 43 - 74, profiles/screen_topk.log
     int64_t screen_chunk_rows = 1 << 22;   // fx_screen_all: rows enumerated, scored and selected per step (a multiple of 16)
     int64_t cnn_quad_tail = 1;  // K1, unrolled seq_len = 8 form: the (tiles mod 4) last tiles of a workgroup are walked by wave quads in one round behind the main loop; 0 = one wave per tile throughout (rounds 1-5)
@@ -331,6 +337,7 @@ struct fx_engine {
     // that averages in-kernel (small launches of the canonical CNN: score_cnn_quad.hip) sets fused_mean_done
     float* fuse_mean_out = nullptr;     // (explorer-size form: option fuse_mean)
     float* fuse_mean_batch_out = nullptr;   // (batch form: option fuse_mean_batch)
+    float* score_table_mean_out = nullptr;  // (the lookup form, score_cnn_lookup.hip: a thread there holds a row's M scores, so the mean costs it one more store)
     bool fused_mean_done = false;
     // resident small-call form (score_cnn_quad.hip / score_dense_small.hip, SERVER): one workgroup per (member, tile slot) stays
     // on the device between explorer-size calls and answers them through the mailboxes above
@@ -455,6 +462,11 @@ struct fx_model {
     // (score_cnn_pooled.hip).  Fresh iff pooltab_version == version: fx_model_set_weights makes it stale without doing any work
     float* d_pooltab = nullptr;
     uint64_t pooltab_version = 0;
+    // ... and the member's SCORE of every possible row, 4^8 floats at the same index (what a scoring launch writes for the row: fx_nan_to_num(y)),
+    // an allocation of its own, built from the pooled-feature table by the head-only kernel (score_cnn_pooled.hip) and read by the lookup kernel
+    // (score_cnn_lookup.hip).  Fresh iff scoretab_version == version
+    float* d_scoretab = nullptr;
+    uint64_t scoretab_version = 0;
     float* d_bytetab = nullptr;
     uint8_t bt_lut[256];
     bool bt_valid = false;
@@ -564,6 +576,14 @@ int fx_build_conv2_prefix(fx_engine* e, fx_model* m);
 // the head-only form of a launch group of canonical seq_len = 8 members (score_cnn_pooled.hip): builds the stale members' tables first when
 // `build`; FX_EUNSUPPORTED (nothing enqueued for the scores) when a table could not be allocated: the caller launches its conv form
 int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
+                               bool build);
+// the members' score tables brought up to date on e->stream (score_cnn_pooled.hip): stale pooled-feature tables are built first when `build_pool`;
+// FX_EUNSUPPORTED when a table is stale and may not be built, or could not be allocated
+int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, bool build_pool);
+// the lookup form of such a launch group (score_cnn_lookup.hip): one table read per row and member, and the ensemble mean where score_then_mean
+// offers its destination and the group is the whole ensemble.  FX_EUNSUPPORTED (nothing enqueued for the scores) when a table could not be had:
+// the caller goes on with the head-only form
+int fx_launch_score_cnn_lookup(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
                                bool build);
 // the conv part of the two-kernel path alone, one 4-letter member: tile-major pooled features into d_pool (score_cnn_split.hip; test hook)
 int fx_launch_cnn_conv_only(fx_engine* e, fx_model* model, const uint8_t* d_ascii, int64_t N, void* d_pool);

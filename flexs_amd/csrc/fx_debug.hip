@@ -155,6 +155,28 @@ int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, 
     out4[1] = pk.id; out4[3] = pk.rc;
     return FX_OK;
 }
+// Host only: ... and about their score tables (fx_cnn_score_decide on that answer; engine option cnn_score_table).  out4 = the CnnScoreDecision (0 what
+// the pooled-table decision names runs, 1 the lookup kernel), the CnnPoolDecision, the pick's CnnFormId, the pick's status.
+int fx_debug_cnn_score_pick(int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host, int fresh,
+                            const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out4) {
+    if (!out4 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
+    fx_engine eng;
+    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    std::memset(out4, 0, 4 * sizeof(int64_t));
+    for (int i = 0; i < n_opts; ++i) {
+        int64_t* slot = nullptr;
+        if (int rc = fx_option_slot_for(&eng, opt_keys[i], opt_values[i], &slot)) return rc;
+        *slot = opt_values[i];
+    }
+    const FxShape s{FX_CNN, L, A, F, H, K};
+    const FxPackLayout lay = fx_pack_layout(s);
+    if (int rc = fx_cnn_fused_supported(&eng, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
+    const CnnPick pk = fx_cnn_pick_fused(&eng, s, lay, N, M);
+    const CnnPoolDecision pool = fx_cnn_pool_decide(&eng, lay, pk, N, fresh != 0);
+    out4[0] = fx_cnn_score_decide(&eng, pool);
+    out4[1] = pool; out4[2] = pk.id; out4[3] = pk.rc;
+    return FX_OK;
+}
 // Needs the GPU: the global-max-pooled conv features of N rows (host memory, N x L bytes) as the CONV-ONLY kernel of the two-kernel path leaves them,
 // row-major (N x 16 FT floats, channel 16 t + 4 g + r at float 16 t + 4 g + r): what the pooled-feature table is held to row by row.
 int fx_debug_cnn_conv_features(fx_model* m, const uint8_t* rows, int64_t N, const uint8_t lut[256], float* out, int64_t cap) {

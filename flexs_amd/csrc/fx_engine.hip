@@ -324,6 +324,7 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "topk_small_rows")) return &e->topk_small_rows;
     if (!std::strcmp(key, "screen_chunk_rows")) return &e->screen_chunk_rows;
     if (!std::strcmp(key, "cnn_pool_table")) return &e->cnn_pool_table;
+    if (!std::strcmp(key, "cnn_score_table")) return &e->cnn_score_table;
     if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
     if (!std::strcmp(key, "cnn_conv2_prefix")) return &e->cnn_conv2_prefix;
     if (!std::strcmp(key, "cnn_head_slab")) return &e->cnn_head_slab;
@@ -391,6 +392,8 @@ int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** s
         return fx_fail(e, FX_EINVAL, "cnn_conv2_prefix is 0 (off) or a depth that is compiled in (1, 2)");
     if (s == &e->cnn_pool_table && (value < 0 || value > 2))
         return fx_fail(e, FX_EINVAL, "cnn_pool_table is 0 (off), 1 (build for launches of more than 4^8 rows) or 2 (build for any launch)");
+    if (s == &e->cnn_score_table && (value < 0 || value > 1))
+        return fx_fail(e, FX_EINVAL, "cnn_score_table is 0 (the head-only kernel scores) or 1 (the members' score tables answer)");
     if (s == &e->topk_small_rows && (value < 0 || value > 8192))
         return fx_fail(e, FX_EINVAL, "topk_small_rows is 0 .. 8192 (what one workgroup sorts in LDS)");
     if (s == &e->screen_chunk_rows && (value < 16 || value > (1 << 26) || (value & 15)))
@@ -436,6 +439,9 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "conv1_table_launches")) { *value = e->counters.conv1_table_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "conv2_prefix_launches")) { *value = e->counters.conv2_prefix_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "pool_table_launches")) { *value = e->counters.pool_table_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "score_table_launches")) { *value = e->counters.score_table_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "score_table_builds")) { *value = e->counters.score_table_builds; return FX_OK; }
+    if (e && key && !std::strcmp(key, "fused_mean_done")) { *value = e->fused_mean_done ? 1 : 0; return FX_OK; }   // (the last score + mean call: 1 = its scoring kernel wrote the mean, no mean launch followed)
     if (e && key && !std::strcmp(key, "topk_large_launches")) { *value = e->counters.topk_large_launches; return FX_OK; }
     if (e && key && !std::strcmp(key, "pool_table_builds")) { *value = e->counters.pool_table_builds; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
@@ -522,6 +528,7 @@ int fx_model_destroy(fx_model* m) {
     if (m->d_packed) (void)hipFree(m->d_packed);
     if (m->d_bytetab) (void)hipFree(m->d_bytetab);
     if (m->d_pooltab) (void)hipFree(m->d_pooltab);
+    if (m->d_scoretab) (void)hipFree(m->d_scoretab);
     delete m;
     return FX_OK;
 }

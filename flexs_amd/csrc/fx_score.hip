@@ -82,10 +82,12 @@ static int score_then_mean(fx_engine* e, fx_model* const* models, int M, const u
                            float* d_planes, int64_t stride, float* mean_dst) {
     e->fuse_mean_out = (e->fuse_mean && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
     e->fuse_mean_batch_out = (e->fuse_mean_batch && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
+    e->score_table_mean_out = (stride && M > 1 && M <= 16) ? mean_dst : nullptr;
     e->fused_mean_done = false;
     const int rc = score_dispatch(e, models, M, d_ascii, N, L, d_planes, stride);
     e->fuse_mean_out = nullptr;
     e->fuse_mean_batch_out = nullptr;
+    e->score_table_mean_out = nullptr;
     if (rc) return rc;
     if (e->fused_mean_done) return FX_OK;
     return fx_launch_ensemble_mean_planar(e, d_planes, N, M, stride, mean_dst);

@@ -356,6 +356,18 @@ inline CnnPoolDecision fx_cnn_pool_decide(const fx_engine* e, const FxPackLayout
     return (e->cnn_pool_table >= 2 || N > FX_POOL_ROWS) ? CNN_POOL_BUILD : CNN_POOL_NO;
 }
 
+// ... and the score itself is a function of the row and the member's weights too: such a member may carry its SCORE for every row as well,
+// FX_POOL_ROWS floats at the same index (fx_model::d_scoretab, built by the head-only kernel over the enumeration of all rows), and a launch is
+// then one table read per row and member (k_score_cnn_mfma_scoretab, score_cnn_lookup.hip).  Engine option cnn_score_table, layered on the
+// answer above: it never makes a launch take a table that cnn_pool_table would not, and never builds where that would not build.
+enum CnnScoreDecision : int {
+    CNN_SCORE_NO = 0,           // what fx_cnn_pool_decide answered runs as without the option: the conv form or the head-only kernel
+    CNN_SCORE_LOOKUP = 1,       // the group's score tables are brought up to date (pooled-feature tables first, as `pool` says), then the lookup kernel
+};
+inline CnnScoreDecision fx_cnn_score_decide(const fx_engine* e, CnnPoolDecision pool) {
+    return (pool != CNN_POOL_NO && e->cnn_score_table >= 1) ? CNN_SCORE_LOOKUP : CNN_SCORE_NO;
+}
+
 // ---------------------------------------------------------------- conv part of the two-kernel path (score_cnn_split.hip)
 inline int fx_cnn_split_supported(const fx_engine* e, const FxShape& s, const FxPackLayout& lay, int M) {
     // (binary alphabet, sequence_utils.py:16's BA: the canonical conv shape only -- its fused kernel covers 97..112 hidden units, this path the rest)

@@ -59,6 +59,11 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
 #if defined(FX_AB)
         if (a.fm_mean) pool = CNN_POOL_NO;
 #endif
+        if (fx_cnn_score_decide(e, pool) == CNN_SCORE_LOOKUP) {
+            // ... or nothing runs but a table read per row and member (score_cnn_lookup.hip)
+            const int rc = fx_launch_score_cnn_lookup(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, pool == CNN_POOL_BUILD);
+            if (rc != FX_EUNSUPPORTED) return rc;       // (no score table could be had: the head-only form)
+        }
         if (pool != CNN_POOL_NO) {
             const int rc = fx_launch_score_cnn_pooled(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, pool == CNN_POOL_BUILD);
             if (rc != FX_EUNSUPPORTED) return rc;       // (no table could be had: the form picked above)

@@ -30,7 +30,10 @@ struct PooledArgs {
     int off_d1, off_d2, off_db, head_floats;   // the head's part of the packed image: [off_d1, off_d1 + head_floats), whole f4
 };
 
-template <int WAVES>
+// ENUM: the builder of a member's score table (fx_model::d_scoretab).  The "batch" is the enumeration of all 4^8 rows, as in the conv kernel's
+// PoolTableBuild form: the codes of lane sq of tile tg are the bits of 16 tg + sq -- no row, no LUT -- and everything behind them is the scoring
+// walk itself, on the same table line: the table holds the bits a scoring launch writes for the row.
+template <int WAVES, bool ENUM>
 __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma_pooled(PooledArgs p) {
     constexpr int FT = 2, HT = 7, L = 8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -77,14 +80,18 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_mfma_pooled(PooledArgs
             if (tg >= s_hi) break;
             asm volatile("" ::: "memory");               // keep the weight reads inside the tile loop
             const int64_t n = tg * 16 + sq;
-            unsigned long long rowq;                      // the whole row is ONE 8-byte load (any alignment); spare lanes of a ragged tile recompute row 0
-            __builtin_memcpy(&rowq, p.ascii + (n < p.N ? n : 0) * L, 8);
             unsigned codes = 0;                           // two bits per letter of the row
+            if constexpr (ENUM) {
+                codes = (unsigned)n;
+            } else {
+                unsigned long long rowq;                  // the whole row is ONE 8-byte load (any alignment); spare lanes of a ragged tile recompute row 0
+                __builtin_memcpy(&rowq, p.ascii + (n < p.N ? n : 0) * L, 8);
 #pragma unroll
-            for (int j = 0; j < L; ++j) {
-                unsigned c = lut_s[(int)((rowq >> (8 * j)) & 0xFFull)];
-                if (c == 0xFF) { bad = true; c = 0; }
-                codes |= c << (2 * j);
+                for (int j = 0; j < L; ++j) {
+                    unsigned c = lut_s[(int)((rowq >> (8 * j)) & 0xFFull)];
+                    if (c == 0xFF) { bad = true; c = 0; }
+                    codes |= c << (2 * j);
+                }
             }
             // the mask keeps the line inside the table whatever the LUT holds
             const char* line = tab + ((size_t)(codes & (unsigned)(FX_POOL_ROWS - 1)) << 7) + ((unsigned)g << 4);
@@ -135,16 +142,15 @@ int build_pool_table(fx_engine* e, fx_model* m) {
     return FX_OK;
 }
 
-}  // namespace
-
-int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
-                               bool build) {
-    constexpr int WAVES = 16;
-    if (N == 0) return FX_OK;
-    const FxPackLayout& lay = models[0]->layout;
+// Whether the head-only kernel serves this shape on this engine, and the LDS it asks for.
+bool pooled_supported(const fx_engine* e, const FxPackLayout& lay, int M, size_t* lds) {
     const int64_t head_floats = lay.total_floats - lay.off_d1;
-    const size_t lds = (size_t)head_floats * 4 + 256 + 48;
-    if (M > FX_MAX_M || lay.off_c1tab < 0 || lay.off_d1 % 4 || head_floats % 4 || lds > (size_t)e->max_lds || e->rows_req.on) return FX_EUNSUPPORTED;
+    *lds = (size_t)head_floats * 4 + 256 + 48;
+    return !(M > FX_MAX_M || lay.off_c1tab < 0 || lay.off_d1 % 4 || head_floats % 4 || *lds > (size_t)e->max_lds || e->rows_req.on);
+}
+
+// Every member's pooled-feature table fresh: the stale ones are built when `build`.  FX_EUNSUPPORTED: one is stale and stays so.
+int fresh_pool_tables(fx_engine* e, fx_model* const* models, int M, bool build) {
     for (int m = 0; m < M; ++m) {
         fx_model* mo = models[m];
         if (mo->d_pooltab && mo->pooltab_version == mo->version) continue;
@@ -156,27 +162,79 @@ int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, con
         }
         if (int rc = build_pool_table(e, mo)) return rc;
     }
-    PooledArgs a{};
-    a.ascii = d_ascii; a.lut = e->d_lut; a.out = d_out_NM; a.err = e->d_err;
+    return FX_OK;
+}
+
+// The head of `lay` on the rows (ENUM: on all 4^8 of them) for the members whose weights and tables `a` names, `blocks` workgroups at the most.
+template <bool ENUM>
+int launch_pooled(fx_engine* e, PooledArgs a, const FxPackLayout& lay, size_t lds, int64_t blocks) {
+    constexpr int WAVES = 16;
+    a.lut = e->d_lut; a.err = e->d_err;
     a.wave_prio = (int)e->wave_prio;
-    for (int m = 0; m < M; ++m) { a.w[m] = models[m]->d_packed; a.tab[m] = models[m]->d_pooltab; }
-    a.N = N; a.TG = (N + 15) / 16; a.M = M; a.m_off = m_off;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    a.TG = (a.N + 15) / 16;
     a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
-    a.off_d1 = (int)lay.off_d1; a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.head_floats = (int)head_floats;
-    auto kern = k_score_cnn_mfma_pooled<WAVES>;
+    a.off_d1 = (int)lay.off_d1; a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.head_floats = (int)(lay.total_floats - lay.off_d1);
+    auto kern = k_score_cnn_mfma_pooled<WAVES, ENUM>;
     static bool attr_set[64] = {};
     if (!attr_set[e->device & 63]) {
         FX_HIP(e, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[e->device & 63] = true;
     }
     const int64_t U = (int64_t)a.M * a.TG;
-    int64_t blocks = e->grid_blocks > 0 ? e->grid_blocks : e->num_cus;
     if (blocks > U) blocks = U;                          // never more workgroups than work units
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), lds, e->stream, a);
     FX_HIP(e, hipGetLastError());
+    return FX_OK;
+}
+
+// One member's score table from its fresh pooled-feature table: the head-only kernel over the enumeration of all rows, on e->stream behind the
+// pooled table's own builder.  Every CU takes part whatever grid_blocks says, as in build_pool_table.
+int build_score_table(fx_engine* e, fx_model* m, size_t lds) {
+    PooledArgs a{};
+    a.w[0] = m->d_packed; a.tab[0] = m->d_pooltab;
+    a.out = m->d_scoretab;
+    a.N = FX_POOL_ROWS; a.M = 1; a.m_off = 0;
+    a.out_sn = 1; a.out_sm = 1;
+    if (int rc = launch_pooled<true>(e, a, m->layout, lds, e->num_cus)) return rc;
+    m->scoretab_version = m->version;
+    e->counters.score_table_builds += 1;
+    return FX_OK;
+}
+
+}  // namespace
+
+int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
+                               bool build) {
+    if (N == 0) return FX_OK;
+    const FxPackLayout& lay = models[0]->layout;
+    size_t lds = 0;
+    if (!pooled_supported(e, lay, M, &lds)) return FX_EUNSUPPORTED;
+    if (int rc = fresh_pool_tables(e, models, M, build)) return rc;
+    PooledArgs a{};
+    a.ascii = d_ascii; a.out = d_out_NM;
+    for (int m = 0; m < M; ++m) { a.w[m] = models[m]->d_packed; a.tab[m] = models[m]->d_pooltab; }
+    a.N = N; a.M = M; a.m_off = m_off;
+    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    if (int rc = launch_pooled<false>(e, a, lay, lds, e->grid_blocks > 0 ? e->grid_blocks : e->num_cus)) return rc;
     e->counters.pool_table_launches += 1;
+    return FX_OK;
+}
+
+int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, bool build_pool) {
+    size_t lds = 0;
+    if (!pooled_supported(e, models[0]->layout, M, &lds)) return FX_EUNSUPPORTED;
+    if (int rc = fresh_pool_tables(e, models, M, build_pool)) return rc;
+    for (int m = 0; m < M; ++m) {
+        fx_model* mo = models[m];
+        if (mo->d_scoretab && mo->scoretab_version == mo->version) continue;
+        if (!mo->d_scoretab && hipMalloc(&mo->d_scoretab, sizeof(float) * (size_t)FX_POOL_ROWS) != hipSuccess) {
+            (void)hipGetLastError();                     // no table: the launch takes the head-only form, without an error
+            mo->d_scoretab = nullptr;
+            return FX_EUNSUPPORTED;
+        }
+        if (int rc = build_score_table(e, mo, lds)) return rc;
+    }
     return FX_OK;
 }
 
@@ -191,4 +249,17 @@ extern "C" int64_t fx_debug_pool_table(fx_model* m, float* out, int64_t cap) {
     FX_HIP(e, hipStreamSynchronize(e->stream));
     FX_HIP(e, hipMemcpy(out, m->d_pooltab, sizeof(float) * 32 * (size_t)FX_POOL_ROWS, hipMemcpyDeviceToHost));
     return (int64_t)32 * FX_POOL_ROWS;
+}
+
+// ... and its score table.  Returns the floats copied; FX_ESTATE: none has been built for the current weights
+extern "C" int64_t fx_debug_score_table(fx_model* m, float* out, int64_t cap) {
+    if (!m || !out) return FX_EINVAL;
+    fx_engine* e = m->eng;
+    if (m->layout.off_c1tab < 0) return FX_EUNSUPPORTED;
+    if (!m->d_scoretab || m->scoretab_version != m->version) return fx_fail(e, FX_ESTATE, "the model has no fresh score table");
+    if (cap < (int64_t)FX_POOL_ROWS) return FX_EINVAL;
+    FX_HIP(e, hipSetDevice(e->device));
+    FX_HIP(e, hipStreamSynchronize(e->stream));
+    FX_HIP(e, hipMemcpy(out, m->d_scoretab, sizeof(float) * (size_t)FX_POOL_ROWS, hipMemcpyDeviceToHost));
+    return (int64_t)FX_POOL_ROWS;
 }

@@ -503,6 +503,10 @@ int64_t fx_debug_conv2_prefix(fx_model *m, int depth, float *out, int64_t cap);
  * of floats copied (cap must hold 2097152), FX_EUNSUPPORTED for shapes without a table, FX_ESTATE when none has been built for
  * the model's current weights (engine option cnn_pool_table). */
 int64_t fx_debug_pool_table(fx_model *m, float *out, int64_t cap);
+/* Needs the GPU: ... and its table of scores (65536 floats at the same row index: what a scoring launch writes for the row).  Returns
+ * the number of floats copied (cap must hold 65536), FX_EUNSUPPORTED for shapes without a table, FX_ESTATE when none has been built
+ * for the model's current weights (engine option cnn_score_table). */
+int64_t fx_debug_score_table(fx_model *m, float *out, int64_t cap);
 /* Needs the GPU: the pooled conv features of N rows (host memory, N x seq_len bytes) as the conv-only kernel of the two-kernel CNN
  * path leaves them, row-major: N x 16 * ceil(F / 16) floats. */
 int fx_debug_cnn_conv_features(fx_model *m, const uint8_t *rows, int64_t N, const uint8_t lut[256], float *out, int64_t cap);
@@ -512,6 +516,11 @@ int fx_debug_cnn_conv_features(fx_model *m, const uint8_t *rows, int64_t N, cons
  * the pick's status}. */
 int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host,
                            int fresh, const char *const *opt_keys, const int64_t *opt_values, int n_opts, int64_t *out4);
+/* Host only: ... and about their score tables under the engine option cnn_score_table (same arguments).  out4 = {0 what
+ * fx_debug_cnn_pool_pick names runs / 1 the lookup kernel answers, after the tables that answer names are built, that answer's
+ * decision, the pick's form id, the pick's status}. */
+int fx_debug_cnn_score_pick(int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host,
+                            int fresh, const char *const *opt_keys, const int64_t *opt_values, int n_opts, int64_t *out4);
 /* Host only: {alloc_floats, dev_floats, off_c1tab, c1tab_floats, off_c2p[0], c2p_floats[0], off_c2p[1], c2p_floats[1]} of the
  * device buffer of a model of this shape (floats; offsets -1 and sizes 0 where the shape carries no table), and the row of a
  * depth's prefix tables that conv position p (0..3) of a seq_len = 8 row reads (codes: two bits per letter, letter i at bits 2i). */
