@@ -604,6 +604,24 @@ class Engine:
                                            _ptr(val), C.byref(n)))
         return idx[:n.value], rows[:n.value], val[:n.value]
 
+    def screen_mutants(self, models: Sequence["NativeModel"], parents_bytes: np.ndarray, alphabet: str, lut: np.ndarray, radius: int, k: int):
+        """The k best among the parents ((P, L) uint8) and all their mutants within Hamming distance `radius` (1 or 2), enumerated on
+        the device in the order of include/flexs_amd.h (fx_screen_mutants): (global row numbers int64 = parent * ball size + row in
+        the ball, (count, L) uint8 rows, scores float32)."""
+        M = len(models)
+        arr = (_vp * M)(*[m.handle for m in models])
+        parents_bytes = np.ascontiguousarray(parents_bytes, np.uint8)
+        P, L = parents_bytes.shape
+        al = np.frombuffer(alphabet.encode("latin-1"), np.uint8).copy()
+        cap = min(max(k, 0), 4096)
+        idx = np.full(cap, -1, np.int64)
+        rows = np.zeros((cap, L), np.uint8)
+        val = np.full(cap, np.nan, np.float32)
+        n = C.c_int(0)
+        self.check(self._lib.fx_screen_mutants(self.handle, arr, M, _ptr(parents_bytes), P, L, al.shape[0], _ptr(al), _lut_ptr(lut), radius, k,
+                                               _ptr(idx), _ptr(rows), _ptr(val), C.byref(n)))
+        return idx[:n.value], rows[:n.value], val[:n.value]
+
     def encode_onehot(self, seq_bytes: np.ndarray, lut: np.ndarray, A: int) -> np.ndarray:
         N, L = seq_bytes.shape
         out = np.empty((N, L, A), np.float32)

@@ -157,6 +157,13 @@ class KerasModel(flexs_amd.Model):
 
         return _screen.screen_all(self, k)
 
+    def screen_mutants(self, parents: SEQUENCES_TYPE, k: int, radius: int = 1):
+        """The k best among `parents` and all their single (radius 1) or single and double (radius 2) mutants, enumerated on the
+        device: (sequences, scores, parent_index) (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen_mutants(self, parents, k, radius)
+
     def _fitness_function(self, sequences):
         """keras_model.py:69-79: encode -> float32 tensor -> predict -> squeeze ->
         nan_to_num, fused on the GPU.  Returns float32 (N,)."""

@@ -220,6 +220,7 @@ struct fx_engine {
         int64_t score_table_launches = 0;   // ... and, of those launch groups, the ones answered by the lookup kernel from the members' score tables (read: option "score_table_launches")
         int64_t score_table_builds = 0;     // score tables built, one per member and build (read: option "score_table_builds")
         int64_t topk_large_launches = 0;    // selects answered by the radix-select form (read: option "topk_large_launches")
+        int64_t mutant_rows_enumerated = 0; // rows written by the mutant enumerator of fx_screen_mutants (read: option "mutant_rows_enumerated")
         int64_t conv2_prefix_launches = 0;  // ... and, of those, the ones that read conv2's first taps from the prefix tables (read: option "conv2_prefix_launches")
     } counters;
     // deferred error word (device) + pinned host mirror
@@ -231,8 +232,9 @@ struct fx_engine {
     uint8_t h_lut[256];
     bool lut_valid = false;
     // growable scratch
-    void* d_scratch[10] = {};   // (5: the relay area of a plain host call, FxRelay; 6 - 9: top-k select and screening, fx_screen.hip)
-    size_t scratch_bytes[10] = {};
+    void* d_scratch[11] = {};   // (5: the relay area of a plain host call, FxRelay; 6 - 9: top-k select and screening, 10: the parents of fx_screen_mutants, fx_screen.hip)
+    size_t scratch_bytes[11] = {};
+    std::vector<uint8_t> mutant_stage;   // fx_screen_mutants: host image of slot 10 (grows to the largest call and stays)
     void* d_train = nullptr;      // fx_train_fit arena (grown on demand, kept between fits)
     size_t train_bytes = 0;
     int64_t train_prof_ns[5] = {};   // the last fx_train_fit: ns since entry at "image filled", "upload enqueued", "launches enqueued", "synchronised", "results copied out"
@@ -723,5 +725,9 @@ int fx_launch_table_lookup(fx_engine* e, const double* d_table, int64_t len, con
 int fx_launch_topk(fx_engine* e, const float* d_scores, int64_t N, int kk, int64_t idx_base, int64_t* d_idx, float* d_val);
 int fx_launch_topk_merge(fx_engine* e, const int64_t* d_gidx, const float* d_vals, int n, int kk, int64_t* d_idx, float* d_val);
 int fx_launch_enumerate_rows(fx_engine* e, uint8_t* d_rows, int64_t row0, int64_t n, int L, int A, const uint8_t* alphabet);
+// rows [row0, row0 + n) of the mutant enumeration of P parents (mutant_rank.h; ball size B) and the 16-byte tail pad behind them, into d_rows (16-byte aligned,
+// n * L + 32 bytes); d_parents / d_codes: P x L ASCII / letter indices, d_alphabet: 256 bytes, all in device memory
+int fx_launch_enumerate_mutants(fx_engine* e, uint8_t* d_rows, int64_t row0, int64_t n, int L, int A, int64_t B, int64_t P,
+                                const uint8_t* d_parents, const uint8_t* d_codes, const uint8_t* d_alphabet);
 int fx_launch_min_dist_finish(fx_engine* e, const unsigned long long* d_keys, int64_t Q, int64_t C,
                               int32_t* d_dist, int64_t* d_arg);

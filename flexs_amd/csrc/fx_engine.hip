@@ -443,6 +443,7 @@ int fx_engine_get_option(fx_engine* e, const char* key, int64_t* value) {
     if (e && key && !std::strcmp(key, "score_table_builds")) { *value = e->counters.score_table_builds; return FX_OK; }
     if (e && key && !std::strcmp(key, "fused_mean_done")) { *value = e->fused_mean_done ? 1 : 0; return FX_OK; }   // (the last score + mean call: 1 = its scoring kernel wrote the mean, no mean launch followed)
     if (e && key && !std::strcmp(key, "topk_large_launches")) { *value = e->counters.topk_large_launches; return FX_OK; }
+    if (e && key && !std::strcmp(key, "mutant_rows_enumerated")) { *value = e->counters.mutant_rows_enumerated; return FX_OK; }
     if (e && key && !std::strcmp(key, "pool_table_builds")) { *value = e->counters.pool_table_builds; return FX_OK; }
     if (e && key && !std::strcmp(key, "launch_relay_calls")) { *value = e->launch_relay_calls; return FX_OK; }
     if (e && key && !std::strcmp(key, "large_bar")) { *value = (e->large_bar && !e->rows_refused) ? 1 : 0; return FX_OK; }   // (the host can store into device memory: resident forms, launched-first calls)

@@ -1,4 +1,5 @@
-// K8: top-k select over float32 scores in device memory, and the row enumerator of fx_screen_all (fx_screen.hip has the ABI).
+// K8: top-k select over float32 scores in device memory, and the row enumerators of fx_screen_all and fx_screen_mutants
+// (fx_screen.hip has the ABI).
 //
 // Every element becomes a 64-bit key (topk_keys.h) whose unsigned order is the whole ordering rule, ties included, and which no
 // other element shares.  Two forms give the k largest keys, largest first:
@@ -15,6 +16,7 @@
 // Nothing here waits for another workgroup: no spin, no grid barrier, no last-block hand-off.
 #include "fx_common.h"
 #include "fx_internal.h"
+#include "mutant_rank.h"
 #include "topk_keys.h"
 
 namespace {
@@ -169,6 +171,25 @@ __global__ __launch_bounds__(256) void k_enumerate_rows(uint8_t* __restrict__ ro
     }
 }
 
+// Rows [row0, row0 + n) of the mutant enumeration (mutant_rank.h: global row = parent * B + local) as ONE FLAT BYTE STREAM: byte b
+// of the chunk is column b % L of row b / L, and a thread produces the 16 consecutive bytes of unit u = b / 16 -- the tail of one
+// row, whole rows where L < 16, the head of the next -- and stores them with one aligned 16-byte store, so a wave writes 1 KiB of
+// consecutive addresses whatever L is (fx_mutant_unit, mutant_rank.h).  Each row piece is the parent's bytes (read through L2: a wave's pieces belong to one or
+// two parents) with the row's at most two changed columns patched.  Units reach past the last row to the end of the 16-byte tail
+// pad the scoring kernels may read: those bytes are the alphabet's first letter.  The caller's buffer holds 16 * units bytes.
+__global__ __launch_bounds__(256) void k_enumerate_mutants(uint4* __restrict__ out, int64_t units, int64_t row0, int64_t n, int L, int A, uint32_t B,
+                                                           const uint8_t* __restrict__ parents, const uint8_t* __restrict__ codes,
+                                                           const uint8_t* __restrict__ alphabet) {
+    __shared__ uint8_t s_al[256];
+    s_al[threadIdx.x] = alphabet[threadIdx.x];
+    __syncthreads();
+    const int64_t step = (int64_t)gridDim.x * 256;
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < units; u += step) {
+        const FxMutantUnit v = fx_mutant_unit(u, row0, n, L, A, B, parents, codes, s_al);
+        out[u] = make_uint4((uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32));
+    }
+}
+
 int grid_for(const fx_engine* e, int64_t N) {
     const int64_t want = (N + 255) / 256, cap = (int64_t)e->num_cus * 8;
     return (int)std::max<int64_t>(1, std::min(want, cap));
@@ -226,5 +247,17 @@ int fx_launch_enumerate_rows(fx_engine* e, uint8_t* d_rows, int64_t row0, int64_
     for (int i = 0; i < 256; ++i) al.c[i] = i < A ? alphabet[i] : 0;
     hipLaunchKernelGGL(k_enumerate_rows, dim3(grid_for(e, n)), dim3(256), 0, e->stream, d_rows, row0, n, L, (unsigned)A, al);
     FX_HIP(e, hipGetLastError());
+    return FX_OK;
+}
+
+int fx_launch_enumerate_mutants(fx_engine* e, uint8_t* d_rows, int64_t row0, int64_t n, int L, int A, int64_t B, int64_t P,
+                                const uint8_t* d_parents, const uint8_t* d_codes, const uint8_t* d_alphabet) {
+    if (n < 1 || L < 1 || A < 1 || A > 256 || B < 1 || P < 1 || row0 < 0 || fx_mutant_total_rows(P, B) < row0 + n || ((uintptr_t)d_rows & 15))
+        return fx_fail(e, FX_EINVAL, "fx_launch_enumerate_mutants: bad sizes");
+    const int64_t units = (n * L + 16 + 15) / 16;          // the rows and the whole 16-byte tail pad: d_rows holds 16 * units <= n * L + 32 bytes
+    hipLaunchKernelGGL(k_enumerate_mutants, dim3(grid_for(e, units)), dim3(256), 0, e->stream, (uint4*)d_rows, units, row0, n, L, A, (uint32_t)B,
+                       d_parents, d_codes, d_alphabet);
+    FX_HIP(e, hipGetLastError());
+    e->counters.mutant_rows_enumerated += n;
     return FX_OK;
 }

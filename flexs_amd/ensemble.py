@@ -92,6 +92,13 @@ class Ensemble(_EnsembleBase):
 
         return _screen.screen_all(self, k)
 
+    def screen_mutants(self, parents: SEQUENCES_TYPE, k: int, radius: int = 1):
+        """The k best among `parents` and all their mutants within Hamming distance `radius` (1 or 2) under the ensemble:
+        (sequences, scores, parent_index) (flexs_amd/utils/screen.py)."""
+        from flexs_amd.utils import screen as _screen
+
+        return _screen.screen_mutants(self, parents, k, radius)
+
     _small = None                                          # explorer-size fast path: (members, fx_models, {want_mean: plan})
 
     def __getstate__(self):

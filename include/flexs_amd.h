@@ -171,7 +171,8 @@ const char *fx_last_error(fx_engine *e);
  *   topk_small_rows   4096     fx_topk* / fx_score_topk* / fx_screen_all: selects over at most this many scores (0 .. 8192) are
  *                              sorted by one workgroup in LDS; larger ones run the radix select (one launch per pass).  Same
  *                              answer either way.  topk_large_launches (read): selects answered by the radix select.
- *   screen_chunk_rows 4194304  fx_screen_all: rows enumerated, scored and selected per step (a multiple of 16, <= 2^26).
+ *   screen_chunk_rows 4194304  fx_screen_all / fx_screen_mutants: rows enumerated, scored and selected per step (a multiple of
+ *                              16, <= 2^26).  mutant_rows_enumerated (read): rows written by the enumerator of fx_screen_mutants.
  *   train_canon       1        fx_train_fit: canonical shapes run the step instantiated with compile-time dimensions
  *                              (k_train_fb 47.8 -> 29.8 us with the padded LDS rows, same bits); 0 = the shape-agnostic
  *                              code for everything.
@@ -326,7 +327,7 @@ int fx_score_mean_planes_dev(fx_engine *e, fx_model *const *models, int M, const
  * FX_ESHAPE; N = 0 gives *out_count = 0; N >= 2^31 gives FX_ESHAPE.  *out_count = min(k, N) is set on return, also by the _dev
  * forms (whose d_idx / d_val are written in stream order).  Values are returned with the bits they have in the input.
  * Engine options: topk_small_rows (selects over at most that many scores are sorted by one workgroup, larger ones run a radix
- * select, one launch per pass; read-only companion topk_large_launches), screen_chunk_rows (fx_screen_all).
+ * select, one launch per pass; read-only companion topk_large_launches), screen_chunk_rows (fx_screen_all, fx_screen_mutants).
  * No allocation per call after the first call of a size. */
 int fx_topk_dev(fx_engine *e, const float *d_scores, int64_t N, int k, int64_t *d_idx, float *d_val, int *out_count);
 int fx_topk(fx_engine *e, const float *scores, int64_t N, int k, int64_t *idx, float *val, int *out_count);
@@ -343,6 +344,21 @@ int fx_score_topk_dev(fx_engine *e, fx_model *const *models, int M, const uint8_
  * go to the lower row number across chunks as within one.  A = the models' alphabet size; A^L > 2^31 - 1: FX_ESHAPE. */
 int fx_screen_all(fx_engine *e, fx_model *const *models, int M, int L, int A, const uint8_t *alphabet,
                   const uint8_t lut[256], int k, int64_t *idx, uint8_t *rows_kxL, float *val, int *out_count);
+/* The local question of a protein surrogate, where A^L is out of reach: the k best among ALL single (radius 1) or single and
+ * double (radius 2) mutants of P parents.  Only the P x L parent bytes go up; the device writes every candidate row itself, chunk
+ * by chunk (screen_chunk_rows), scores it, and keeps the best k as fx_screen_all does.  The ball of a parent s is, in this order:
+ * s itself; then for d = 1 .. radius, for the positions in the order of itertools.combinations(range(L), d), for the letters in
+ * the order of itertools.product over, per changed position, the alphabet without the parent's own letter there (last position
+ * fastest): s with those positions set to those letters.  Ball size B = 1 + L (A - 1), plus C(L, 2) (A - 1)^2 for radius 2;
+ * global row = parent number * B + row within the ball; idx = the winners' global rows (parent number = idx / B), rows_kxL their
+ * bytes (rebuilt on the host from idx: no row of a loser leaves the device), val their scores.  Duplicates -- across parents, or a
+ * parent listed twice -- are kept: their scores tie and the lower global row wins, by the ordering rule above.
+ * FX_ESHAPE: radius outside {1, 2}, P < 1, P * B > 2^31 - 1, k outside 1 .. 4096, A not the models' alphabet size.  A parent
+ * byte outside the LUT: FX_EBADCHAR, checked on the host before any launch, nothing written.  alphabet[a] must be the byte the
+ * LUT maps to a.  Read-only engine option mutant_rows_enumerated: rows written by the enumerator since the engine was created. */
+int fx_screen_mutants(fx_engine *e, fx_model *const *models, int M, const uint8_t *parents_PxL, int64_t P, int L, int A,
+                      const uint8_t *alphabet, const uint8_t lut[256], int radius, int k, int64_t *idx, uint8_t *rows_kxL,
+                      float *val, int *out_count);
 
 /* string_to_one_hot over a batch (sequence_utils.py:32-47 + keras_model.py:70-75):
  * N x L bytes -> N x L x A float32 0/1.  Stand-alone, HBM-bound. */
