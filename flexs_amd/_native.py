@@ -356,8 +356,11 @@ class Engine:
         return pool
 
     # ---- options / sync / timing
+    options_gen = 0                 # bumped by every set_option: callers that cache an option's value (DistributedEnsemble: step_call) compare this
+
     def set_option(self, key: str, value: int):
         self.check(self._lib.fx_engine_set_option(self.handle, key.encode(), int(value)))
+        self.options_gen += 1
 
     def get_option(self, key: str) -> int:
         v = C.c_int64()
@@ -782,6 +785,44 @@ class NativeModel:
             if self.handle:
                 self.engine._lib.fx_model_destroy(self.handle)
                 self.handle = None
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class NativeStep:
+    """fx_step handle: one scoring step prepared for repeated launches (include/flexs_amd.h, "prepared step").  Members, seq_len, LUT,
+    planes, stride and the mean / error-word destinations are validated and handed over once; `launch(d_ascii, N)` is then one short
+    ctypes call that enqueues what `Engine.score_mean_planes_dev` (a mean destination given) or `Engine.score_planes_dev` (none)
+    enqueue, followed by `Engine.error_word_dev` where an error-word destination was given.  Holds its `NativeModel`s, so that they
+    outlive it; the caller keeps the buffers alive."""
+
+    def __init__(self, engine: Engine, models: Sequence["NativeModel"], L: int, lut: np.ndarray, d_planes: int, stride: int,
+                 d_mean: Optional[int] = None, d_err_word: Optional[int] = None):
+        self.engine = engine
+        self.models = list(models)
+        M = len(self.models)
+        arr = (_vp * M)(*[m.handle for m in self.models])
+        h = _vp()
+        engine.check(engine._lib.fx_step_create(engine.handle, arr, M, L, _lut_ptr(lut), _vp(d_planes) if d_planes else None, stride,
+                                                _vp(d_mean) if d_mean else None, _vp(d_err_word) if d_err_word else None, C.byref(h)))
+        self.handle = h
+        self._h = h.value
+        self._launch = engine._lib.fx_step_launch
+
+    def launch(self, d_ascii: int, N: int):
+        rc = self._launch(self._h, d_ascii, N)
+        if rc:
+            _raise(rc, self.engine.handle)
+
+    def destroy(self):
+        if self.handle:
+            self.engine._lib.fx_step_destroy(self.handle)
+            self.handle = None
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
         except Exception:  # noqa: BLE001 - interpreter shutdown
             pass
 

@@ -119,6 +119,9 @@ struct FxPackLayout {
 #ifndef FX_POOL_TABLE_DEFAULT
 #define FX_POOL_TABLE_DEFAULT 1 // engine option cnn_pool_table as shipped (profiles/pool_table_ab.log; -DFX_POOL_TABLE_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
 #endif
+#ifndef FX_STEP_CALL_DEFAULT
+#define FX_STEP_CALL_DEFAULT 1  // engine option step_call as shipped (profiles/step_issue_ab.log; -DFX_STEP_CALL_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
+#endif
 #ifndef FX_SCORE_TABLE_DEFAULT
 #define FX_SCORE_TABLE_DEFAULT 1 // engine option cnn_score_table as shipped (profiles/score_table_ab.log; -DFX_SCORE_TABLE_DEFAULT=0 on fx_engine.hip: the A/B arm of bench.py)
 #endif
@@ -231,6 +234,10 @@ struct fx_engine {
     uint8_t* d_lut = nullptr;
     uint8_t h_lut[256];
     bool lut_valid = false;
+    uint64_t lut_gen = 0;       // bumped by every fx_upload_lut that uploads another LUT: a prepared step that has seen this generation knows d_lut is still its own
+    // prepared steps (fx_step.hip): the live ones, so that fx_model_destroy / fx_engine_destroy can mark those that refer to them dead
+    std::vector<struct fx_step*> steps;
+    int64_t step_call = FX_STEP_CALL_DEFAULT;   // read by the callers above the ABI (flexs_amd/distributed.py): 1 = a resident launch / finish step is issued through a prepared step (fx_step_create once per slot, fx_step_launch per step); 0 = through the direct calls (fx_score_mean_planes_dev / fx_score_planes_dev + fx_engine_error_word_dev), as before: A/B.  Same kernels, same bits
     // growable scratch
     void* d_scratch[11] = {};   // (5: the relay area of a plain host call, FxRelay; 6 - 9: top-k select and screening, 10: the parents of fx_screen_mutants, fx_screen.hip)
     size_t scratch_bytes[11] = {};

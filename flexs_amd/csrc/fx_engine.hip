@@ -105,6 +105,7 @@ int fx_upload_lut(fx_engine* e, const uint8_t lut[256]) {
     // a later call with a different LUT must not overwrite h_lut while this copy is pending
     FX_HIP(e, hipStreamSynchronize(e->stream));
     e->lut_valid = true;
+    e->lut_gen += 1;
     return FX_OK;
 }
 
@@ -129,6 +130,12 @@ __global__ void k_error_word(const unsigned* err, float* dst) {
     unsigned v = 0;
     for (int i = 0; i < FX_ERR_WORDS; ++i) v |= __hip_atomic_load(err + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     *dst = (float)v;
+}
+// (shared by fx_engine_error_word_dev and a prepared step that carries an error-word destination, fx_step.hip)
+int fx_launch_error_word(fx_engine* e, float* d_dst) {
+    hipLaunchKernelGGL(k_error_word, dim3(1), dim3(1), 0, e->stream, e->d_err, d_dst);
+    FX_HIP(e, hipGetLastError());
+    return FX_OK;
 }
 
 int check_deferred(fx_engine* e) {
@@ -234,6 +241,7 @@ int fx_engine_destroy(fx_engine* e) {
         e->server.h_out = nullptr;
     }
     fx_lp_disarm(e);
+    fx_steps_forget_engine(e);                             // (its prepared steps stay the caller's to destroy, but are dead)
     (void)hipStreamSynchronize(e->stream);
     for (auto& p : e->d_scratch) if (p) (void)hipFree(p);
     if (e->d_zero_pool) (void)hipFree(e->d_zero_pool);
@@ -284,9 +292,7 @@ int fx_engine_sync(fx_engine* e) {
 int fx_engine_error_word_dev(fx_engine* e, float* d_dst) {
     if (!e || !d_dst) return FX_EINVAL;
     FX_HIP(e, hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_error_word, dim3(1), dim3(1), 0, e->stream, e->d_err, d_dst);
-    FX_HIP(e, hipGetLastError());
-    return FX_OK;
+    return fx_launch_error_word(e, d_dst);
 }
 
 const char* fx_last_error(fx_engine* e) { return e ? e->last_error.c_str() : g_last_error_noengine.c_str(); }
@@ -325,6 +331,7 @@ static int64_t* option_slot(fx_engine* e, const char* key) {
     if (!std::strcmp(key, "screen_chunk_rows")) return &e->screen_chunk_rows;
     if (!std::strcmp(key, "cnn_pool_table")) return &e->cnn_pool_table;
     if (!std::strcmp(key, "cnn_score_table")) return &e->cnn_score_table;
+    if (!std::strcmp(key, "step_call")) return &e->step_call;
     if (!std::strcmp(key, "cnn_conv1_table")) return &e->cnn_conv1_table;
     if (!std::strcmp(key, "cnn_conv2_prefix")) return &e->cnn_conv2_prefix;
     if (!std::strcmp(key, "cnn_head_slab")) return &e->cnn_head_slab;
@@ -394,6 +401,8 @@ int fx_option_slot_for(fx_engine* e, const char* key, int64_t value, int64_t** s
         return fx_fail(e, FX_EINVAL, "cnn_pool_table is 0 (off), 1 (build for launches of more than 4^8 rows) or 2 (build for any launch)");
     if (s == &e->cnn_score_table && (value < 0 || value > 1))
         return fx_fail(e, FX_EINVAL, "cnn_score_table is 0 (the head-only kernel scores) or 1 (the members' score tables answer)");
+    if (s == &e->step_call && (value < 0 || value > 1))
+        return fx_fail(e, FX_EINVAL, "step_call is 0 (the direct scoring calls) or 1 (a prepared step per slot)");
     if (s == &e->topk_small_rows && (value < 0 || value > 8192))
         return fx_fail(e, FX_EINVAL, "topk_small_rows is 0 .. 8192 (what one workgroup sorts in LDS)");
     if (s == &e->screen_chunk_rows && (value < 16 || value > (1 << 26) || (value & 15)))
@@ -524,6 +533,7 @@ int fx_model_destroy(fx_model* m) {
         sv.pending.clear();
         sv.refused.clear();
     }
+    fx_steps_forget_model(m);                              // (prepared steps that hold this handle are dead from here on)
     (void)hipStreamSynchronize(m->eng->stream);
     if (m->d_blob) (void)hipFree(m->d_blob);
     if (m->d_packed) (void)hipFree(m->d_packed);

@@ -35,4 +35,8 @@ FXI void server_stop(fx_engine* e);      // fx_resident.hip
 FXI int wait_for_results(fx_engine* e, unsigned want_seq = 0);      // fx_resident.hip
 FXI int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L, float* d_NM, int64_t planar_stride = 0);      // fx_score.hip
 FXI int validate_models(fx_engine* e, fx_model* const* models, int M, int L, const uint8_t* lut);      // fx_score.hip
+FXI int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L, float* d_planes, int64_t stride, float* mean_dst);      // fx_score.hip
+FXI int fx_launch_error_word(fx_engine* e, float* d_dst);      // fx_engine.hip
+FXI void fx_steps_forget_model(fx_model* m);      // fx_step.hip: the prepared steps that hold `m` are dead from here on
+FXI void fx_steps_forget_engine(fx_engine* e);      // fx_step.hip: ... every prepared step of `e`
 }  // extern "C"

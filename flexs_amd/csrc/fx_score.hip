@@ -78,8 +78,8 @@ int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* 
 }
 
 // score into member-major planes, then the NumPy-order mean -- in the scoring kernel itself where a launcher offers it
-static int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L,
-                           float* d_planes, int64_t stride, float* mean_dst) {
+int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L,
+                    float* d_planes, int64_t stride, float* mean_dst) {
     e->fuse_mean_out = (e->fuse_mean && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
     e->fuse_mean_batch_out = (e->fuse_mean_batch && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
     e->score_table_mean_out = (stride && M > 1 && M <= 16) ? mean_dst : nullptr;

@@ -108,6 +108,10 @@ class _Slot:
         self.busy = False
         self.keep = None
         self.err = None             # (injected scorer only) the ValueError this rank's scorer raised
+        # what stays the same from step to step of this slot, rebuilt only when it stops being so:
+        self.out = None             # what `finish` hands out for want = "mean" with one rank: s.recv.view(-1)[:n] (rebuilt with the key)
+        self.step = None            # the scoring call as a prepared `_native.NativeStep` (engine option step_call = 1) ...
+        self.step_for = None        # ... and what it was prepared for: (NativeModel handles, LUT array, with mean, with error word)
 
 
 class DistributedEnsemble(flexs_amd.Model):
@@ -150,6 +154,7 @@ class DistributedEnsemble(flexs_amd.Model):
         self._host_exchange = self._cuda and not _on_gpu(group)
         self._slots = [_Slot(), _Slot()]
         self._comm = None
+        self._step_call = (None, -1, False)                        # (engine, its options_gen, option step_call) as last read
         # with one rank the gathered block IS the local block (no copy, no second stream); tests and
         # `bench.py --force-dist` set this to run the real collective on a one-rank RCCL group
         self.force_collective = False
@@ -163,9 +168,27 @@ class DistributedEnsemble(flexs_amd.Model):
         """Compute stream of the device path: the torch stream the scoring engine enqueues on."""
         return self._engine().torch_stream() if self._cuda else None
 
-    def _shape(self, n: int, want: str):
+    def _use_step(self, eng) -> bool:
+        """Engine option step_call (csrc/OPTIONS.md), read again only after a `set_option` on the engine."""
+        c = self._step_call
+        if c[0] is not eng or c[1] != eng.options_gen:
+            c = self._step_call = (eng, eng.options_gen, eng.get_option("step_call") != 0)
+        return c[2]
+
+    def _prepared(self, s: "_Slot", eng, natives, lut, L: int, stride: int, mean: bool, err_word: bool):
+        """The slot's `NativeStep` for these members and buffers; prepared again only when the `NativeModel` handles, the members' LUT
+        array or the destinations are no longer the ones it was prepared for (the slot's buffers change with its key, which drops it)."""
+        f = s.step_for
+        if f is None or f[0] != natives or f[1] is not lut or f[2] != mean or f[3] != err_word:
+            s.step = _native.NativeStep(eng, natives, L, lut, s.planes.data_ptr(), stride, s.local.data_ptr() if mean else None,
+                                        s.local.data_ptr() + 4 * (stride - 1) if err_word else None)
+            s.step_for = (natives, lut, mean, err_word)
+        return s.step
+
+    def _shape(self, n: int, want: str, rank: Optional[int] = None, world: Optional[int] = None):
         """(members scored here, rows scored here [lo, hi), planes gathered per rank, plane stride) for a batch."""
-        rank, world = _world(self.group)
+        if world is None:
+            rank, world = _world(self.group)
         M = len(self.models)
         if self.mode == "member":
             return member_assignment(M, rank, world), (0, n), -(-M // world), _stride_for(n)
@@ -293,11 +316,12 @@ class DistributedEnsemble(flexs_amd.Model):
         rank, world = _world(self.group)
         n = int(seq.shape[0]) if n is None else n
         M = len(self.models)
-        mine, (lo, hi), per, stride = self._shape(n, want)
+        mine, (lo, hi), per, stride = self._shape(n, want, rank, world)
         s = self._slots[slot]
-        dev = torch.device("cuda", torch.cuda.current_device()) if self._cuda else torch.device("cpu")
         key = (n, per, stride, world, want)
         if s.key != key:
+            dev = torch.device("cuda", torch.cuda.current_device()) if self._cuda else torch.device("cpu")
+            s.step = s.step_for = None                             # (prepared for the buffers that go away here)
             s.local = torch.zeros((per, stride), dtype=torch.float32, device=dev)
             s.exchange = world > 1 or (self.force_collective and dist.is_available() and dist.is_initialized())
             s.recv = torch.zeros((world, per, stride), dtype=torch.float32, device=dev) if s.exchange else s.local.unsqueeze(0)
@@ -306,57 +330,71 @@ class DistributedEnsemble(flexs_amd.Model):
             local_reduce = self.mode == "sequence" and want == "mean"
             s.planes = torch.zeros((M, stride), dtype=torch.float32, device=dev) if local_reduce else s.local
             s.done = torch.cuda.Event() if self._cuda else None
+            # one rank, sequence mode, mean: the "gathered" means are the local ones, one view for every step of this key
+            s.out = s.recv.view(-1)[:n] if (self.mode == "sequence" and want == "mean" and world == 1) else None
             s.key, s.busy = key, False
             if self._cuda:
                 torch.cuda.current_stream().synchronize()            # the zero fills ran on the caller's stream
         s.n, s.want = n, want
         local_reduce = s.planes is not s.local
         if self._cuda:
+            # The engine's calls name their stream themselves; a `torch.cuda.stream` context is entered only where a torch op is
+            # enqueued (the upload of a NumPy batch, the transpose of the M > 16 mean, the exchange).  A resident batch scored by
+            # one rank enqueues none: its step is `native()` per member + one short native call (`_native.NativeStep`).
             m0 = self.models[0]
-            st = self.stream
+            eng = self._engine()
+            st = eng.torch_stream()
             if self._comm is None:
                 self._comm = torch.cuda.Stream()
-            with torch.cuda.stream(st):
-                if s.busy and s.exchange and not self._host_exchange:
-                    st.wait_event(s.done)                            # the slot's previous gather has been consumed
-                if isinstance(seq, np.ndarray):
-                    seq = torch.from_numpy(np.ascontiguousarray(seq[lo:hi])).to(dev, non_blocking=True)
-                    row0 = 0
+            if s.busy and s.exchange and not self._host_exchange:
+                st.wait_event(s.done)                                # the slot's previous gather has been consumed
+            if isinstance(seq, np.ndarray):
+                with torch.cuda.stream(st):
+                    seq = torch.from_numpy(np.ascontiguousarray(seq[lo:hi])).to(s.local.device, non_blocking=True)
+                row0 = 0
+            else:
+                row0 = lo
+            # the error word travels WITH the scores: a character outside the alphabet fails the call on every rank
+            # (sequence_utils.py:46 raises for the whole batch) without a second collective or a host sync
+            err_word = s.exchange
+            if mine and hi > lo:
+                natives = [self.models[i].native() for i in mine]    # (per step: this is what uploads new weights)
+                L = m0.model.L
+                mean_too = local_reduce and M <= 16
+                # (an event pair brackets the scoring call alone: a timed step that also sends an error word takes the direct calls)
+                step = self._use_step(eng) and not (timing and err_word) and (mean_too or not local_reduce)
+                if timing:
+                    timing[0].record(st)
+                if step:
+                    # the scoring call (+ the error word behind it) as prepared for this slot: same planner, same kernels
+                    self._prepared(s, eng, natives, m0._lut, L, stride, mean_too, err_word).launch(seq.data_ptr() + row0 * L, hi - lo)
+                    err_word = False
+                elif mean_too:
+                    # scores + their NumPy-order mean in one call: the scoring kernel averages a tile itself where it can
+                    # (the last member to finish it), otherwise the mean kernel follows inside the call
+                    eng.score_mean_planes_dev(natives, seq.data_ptr() + row0 * L, hi - lo, L, m0._lut, s.planes.data_ptr(), stride,
+                                              s.local.data_ptr())
                 else:
-                    row0 = lo
-                if mine and hi > lo:
-                    natives = [self.models[i].native() for i in mine]
-                    if timing:
-                        timing[0].record(st)
-                    if local_reduce and M <= 16:
-                        # scores + their NumPy-order mean in one call: the scoring kernel averages a tile itself where it can
-                        # (the last member to finish it), otherwise the mean kernel follows inside the call
-                        self._engine().score_mean_planes_dev(natives, seq.data_ptr() + row0 * m0.model.L, hi - lo, m0.model.L,
-                                                             m0._lut, s.planes.data_ptr(), stride, s.local.data_ptr())
-                        if timing:
-                            timing[1].record(st)
-                    else:
-                        self._engine().score_planes_dev(natives, seq.data_ptr() + row0 * m0.model.L, hi - lo, m0.model.L,
-                                                        m0._lut, s.planes.data_ptr(), stride)
-                        if timing:
-                            timing[1].record(st)
-                        if local_reduce:
-                            self._reduce_planes(s.planes, hi - lo, M, stride, s.local)
-                if s.exchange:
-                    # the error word travels WITH the scores: a character outside the alphabet fails the call on every rank
-                    # (sequence_utils.py:46 raises for the whole batch) without a second collective or a host sync
-                    self._engine().error_word_dev(s.local.data_ptr() + 4 * (stride - 1))
-                s.keep = seq                                         # alive until the kernels have run
-                if s.exchange and self._host_exchange:
+                    eng.score_planes_dev(natives, seq.data_ptr() + row0 * L, hi - lo, L, m0._lut, s.planes.data_ptr(), stride)
+                if timing:
+                    timing[1].record(st)
+                if local_reduce and not mean_too:
+                    with torch.cuda.stream(st):
+                        self._reduce_planes(s.planes, hi - lo, M, stride, s.local)
+            if err_word:
+                eng.error_word_dev(s.local.data_ptr() + 4 * (stride - 1))
+            s.keep = seq                                             # alive until the kernels have run
+            if s.exchange and self._host_exchange:
+                with torch.cuda.stream(st):
                     host = s.local.cpu()                             # (stream-ordered, synchronous D2H)
                     got = torch.empty((world,) + tuple(host.shape), dtype=torch.float32)
                     _all_gather(got, host, self.group, force=True)   # gloo: the list form on host tensors
                     s.recv.copy_(got)
-                elif s.exchange:
-                    self._comm.wait_stream(st)
-                    with torch.cuda.stream(self._comm):
-                        _all_gather(s.recv, s.local, self.group, force=True)   # RCCL over xGMI, device buffers
-                        s.done.record(self._comm)
+            elif s.exchange:
+                self._comm.wait_stream(st)
+                with torch.cuda.stream(self._comm):
+                    _all_gather(s.recv, s.local, self.group, force=True)   # RCCL over xGMI, device buffers
+                    s.done.record(self._comm)
         else:
             b = np.ascontiguousarray(seq[lo:hi])
             s.err = None
@@ -378,13 +416,14 @@ class DistributedEnsemble(flexs_amd.Model):
         """Wait for the slot's gather and hand out what `launch` was asked for: the `(n,)` np.mean-order mean, or the
         stacked `(n, M)` predictions (`np.stack(axis=1)` of ensemble.py:55-57) -- on every rank, as a tensor on the
         gather device (CUDA on RCCL); the caller decides when to copy it to the host."""
-        rank, world = _world(self.group)
         s = self._slots[slot]
         n, M, want = s.n, len(self.models), s.want
-        _, per, stride, _, _ = s.key
+        _, per, stride, world, _ = s.key                             # (the world `launch` saw)
         if self._cuda and s.exchange and not self._host_exchange:
             self.stream.wait_event(s.done)
         s.busy = False
+        if s.out is not None:
+            return s.out                                             # one rank's means: nothing to enqueue, the view is the slot's
         with (torch.cuda.stream(self.stream) if self._cuda else _Null()):
             if self.mode == "member":
                 planes = s.recv.view(world * per, stride)            # plane p = member p (contiguous assignment)

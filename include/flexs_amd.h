@@ -317,6 +317,27 @@ int fx_ensemble_mean_planes_dev(fx_engine *e, const float *d_planes, int64_t N, 
  * launched (engine option "fuse_mean_batch", default 1); same bits either way.  M <= 16. */
 int fx_score_mean_planes_dev(fx_engine *e, fx_model *const *models, int M, const uint8_t *d_ascii, int64_t N,
                              int L, const uint8_t lut[256], float *d_planes, int64_t stride, float *d_out_mean);
+/* ------------------------------------------------------------- prepared step
+ * For a caller that streams batches through the same members into the same buffers (flexs_amd/distributed.py, one step per
+ * slot): everything that stays the same between two steps is handed over ONCE and a step is then issued with (rows, N).
+ *   fx_step_create   validates as fx_score_mean_planes_dev (d_mean given; M <= 16) or fx_score_planes_dev (d_mean NULL) do --
+ *                    members, seq_len, alphabet sizes, the LUT's range, stride a multiple of 4, planes 16-byte aligned --
+ *                    copies the LUT and keeps the member handles.  d_err_word may be NULL.
+ *   fx_step_launch   enqueues on the engine's stream, in this order, exactly what the direct calls enqueue for the same
+ *                    arguments: fx_score_mean_planes_dev (or fx_score_planes_dev) for N rows at d_ascii, then, where
+ *                    d_err_word was given, fx_engine_error_word_dev.  0 <= N <= stride, N may differ from call to call;
+ *                    N = 0 enqueues nothing but the error word.  Same planner, same kernel forms, same bits, same counters
+ *                    as the direct calls.  Per call only what can go stale is checked: the members are alive, belong to the
+ *                    engine and have weights (new weights are picked up as by any call); the engine's device LUT is still
+ *                    this step's (re-uploaded if another call changed it).
+ *   lifetime         fx_model_destroy of a member and fx_engine_destroy make the step DEAD: fx_step_launch then returns
+ *                    FX_ESTATE and enqueues nothing.  fx_step_destroy frees the step, before or after either of them.
+ * The engine option "step_call" (default 1; csrc/OPTIONS.md) tells the callers above this ABI which of the two ways to use. */
+typedef struct fx_step fx_step;
+int fx_step_create(fx_engine *e, fx_model *const *models, int M, int L, const uint8_t lut[256], float *d_planes,
+                   int64_t stride, float *d_mean, float *d_err_word, fx_step **out);
+int fx_step_launch(fx_step *step, const uint8_t *d_ascii, int64_t N);
+int fx_step_destroy(fx_step *step);
 
 /* ---------------------------------------------------------------- screening
  * What every consumer of `get_fitness` does next -- `np.argsort(preds)[: -batch : -1]` (adalead.py:173, cmaes.py:120,
