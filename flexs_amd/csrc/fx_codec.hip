@@ -145,7 +145,9 @@ int fx_decode_score(fx_engine* e, fx_model* const* models, int M, const double* 
         float* z_mean = (float*)(z.d_out + nm_bytes);
         uint8_t* z_chars = (uint8_t*)(z.d_out + o_chars);
         if ((rc = fx_launch_argmax_decode(e, (const double*)z.d_in, rows, A, (const uint8_t*)(z.d_in + in_bytes), z_chars))) return rc;
-        if ((rc = score_dispatch(e, models, M, z_chars, P, L, z_NM))) return rc;
+        // (the default request: z_chars is pinned host memory, and host rows are NOT stated -- deliberate parity with what this call has always asked for, not a claim that it is best)
+        FxOutcome out;
+        if ((rc = score_dispatch(e, models, M, z_chars, P, z_NM, FxRequest{}, out))) return rc;
         if (out_mean && (rc = fx_launch_ensemble_reduce(e, z_NM, P, M, nullptr, z_mean, nullptr))) return rc;
         if ((rc = fx_wait_small(e))) return rc;          // (a completion value polled in pinned memory: wait_for_results)
         if (out_mean) std::memcpy(out_mean, z.h_out + nm_bytes, mean_bytes);
@@ -164,7 +166,8 @@ int fx_decode_score(fx_engine* e, fx_model* const* models, int M, const double* 
     FX_HIP(e, hipMemcpyAsync(d_al, alphabet, (size_t)A, hipMemcpyHostToDevice, e->stream));
     if ((rc = fx_upload_lut(e, lut))) return rc;
     if ((rc = fx_launch_argmax_decode(e, (const double*)d_in, rows, A, d_al, d_chars))) return rc;
-    if ((rc = score_dispatch(e, models, M, d_chars, P, L, d_NM))) return rc;
+    FxOutcome out;
+    if ((rc = score_dispatch(e, models, M, d_chars, P, d_NM, FxRequest{}, out))) return rc;
     if (out_mean) {
         if ((rc = fx_launch_ensemble_reduce(e, d_NM, P, M, nullptr, d_mean, nullptr))) return rc;
         FX_HIP(e, hipMemcpyAsync(out_mean, d_mean, mean_bytes, hipMemcpyDeviceToHost, e->stream));

@@ -46,6 +46,46 @@ struct FxRowsReady {
     int Q;                      // number of stages
     int pitch;                  // bytes from one tile's rows to the next tile's
 };
+
+// What ONE dispatch (score_dispatch / score_then_mean, fx_score.hip) is asked for: built by the entry point on its own stack, const to
+// the planner, the launchers and the form choices below it.  The default is a bare dispatch: rows in device memory, all there, the
+// row-major (N, M) matrix of the ABI, no mean, an ordinary launch.
+struct FxRequest {
+    int64_t stride = 0;         // layout of the scores: 0 = row-major (N, M) (np.stack axis=1); > 0 = member-major planes that many floats apart
+                                // (the engine's own intermediate when only the mean is wanted: a unit's 16 scores are one 64-byte store)
+    bool host_rows = false;     // the sequences are read from pinned HOST memory (zero-copy host calls)
+    float* mean_out = nullptr;  // score_then_mean: where the ensemble mean goes (set when stride && 1 < M <= 16).  A launcher that can average
+                                // in-kernel adds its own option test and says so in FxOutcome::mean_done; otherwise the mean kernel follows
+    bool arm_next = false;      // launch_lp: make this launch a pre-launched instance (fx_resident.hip lp_arm)
+    // launched-first host call (fx_score_begin_staged): what the launchers that can wait for rows copy into their arguments (a launcher
+    // that cannot returns FX_EUNSUPPORTED before it enqueues anything)
+    bool rows_on = false;
+    FxRowsReady rows = {nullptr, 0, 0, 0, 0};             // (Q: the launcher's, fx_rows_plan)
+    FxRelay relay = {nullptr, nullptr, 0, 0, 0};
+    int64_t min_share = 0;      // tiles in the shortest per-SIMD share of the launch
+};
+// ... and what the dispatch did: zeroed by score_dispatch, filled by the launchers.
+struct FxOutcome {
+    bool rows_used = false;     // the launch enqueued waits for its rows (FxRequest::rows) ...
+    bool relay_used = false;    // ... and passes them on (FxRequest::relay)
+    int Q = 0;                  // ... in this many stages
+    bool mean_done = false;     // the scoring kernel wrote FxRequest::mean_out: no mean launch follows
+    int lp_launches = 0;        // launch_lp calls
+    int groups = 0;             // launch groups
+};
+// out[n * out_sn + (m_off + m) * out_sm]: the strides of the request's layout, for every launcher's argument struct
+template <class Args>
+inline void fx_out_strides(Args& a, const FxRequest& rq, int Mtot) {
+    a.out_sn = rq.stride ? 1 : Mtot;
+    a.out_sm = rq.stride ? rq.stride : 1;
+}
+// The launcher's part of a launched-first call's plan: as many stages as the shortest per-SIMD share has tiles.  0 = too few to
+// order (nothing launched).
+inline int fx_rows_plan(int64_t min_share) {
+    const int64_t Q = min_share > 2048 ? 2048 : min_share;
+    return Q < 2 ? 0 : (int)Q;
+}
+
 // The resident form (score_cnn_quad.hip / score_dense_small.hip, SERVER).  Round 3: <= 16 tile slots per member on a third
 // of the CUs, one tile per slot and request -> 256 sequences.  Round 4 (engine option serve_wide): a generation may take
 // most of the chip -- up to FX_SERVE_TILES slots per member -- and a slot walks the tiles slot, slot + T, slot + 2T, ... of a
@@ -289,7 +329,9 @@ struct fx_engine {
     // Completion flag (round 4): a kernel form that can tell when its LAST result has been written stores done_seq into a word
     // of pinned host memory, and a small host call polls that word instead of hipStreamSynchronize -- launch-to-"the host
     // knows" beyond the kernel's own time 11.1 -> 6.0 us (tools/probes/sync_latency_probe.hip).  done_armed: the last launch of
-    // the current dispatch does so (cleared before every launch group, set by the launcher).
+    // the current dispatch does so (cleared before every launch group, set by the launcher).  These three stay on the engine, not in a
+    // dispatch's FxOutcome: they describe the STREAM -- whether the last thing enqueued raises the completion word -- and
+    // wait_for_results / fx_wait_small consume them long after the dispatch has returned (fx_nam.hip too).
     unsigned* h_done = nullptr; unsigned* d_done = nullptr;
     unsigned done_seq = 0;
     unsigned done_value = 0;         // last value handed to hipStreamWriteValue32 (h_done[8]): launches without a kernel-side flag
@@ -311,9 +353,6 @@ struct fx_engine {
         const void* out_dev = nullptr; const void* scratch2 = nullptr; const void* zero_pool = nullptr;   // buffers baked into the armed launch (round-4 advisor: compared, not assumed)
         std::chrono::steady_clock::time_point t{};
     } lp_armed;
-    bool lp_arm_next = false;        // launch_lp: make this launch a pre-launched instance
-    int lp_launches = 0;             // launch_lp calls of the current dispatch
-    int dispatch_groups = 0;         // launch groups of the current dispatch
     int64_t lp_prelaunch = 1;        // option: 1 = pre-launch the next instance after an explorer-size call of the layer-parallel form (0 = never: A/B)
     int64_t lp_armed_served = 0;     // (read) calls answered by a pre-launched instance
     int64_t done_flag = 1;           // option: 1 = poll the completion flag where a kernel offers one, 0 = always hipStreamSynchronize (A/B)
@@ -338,15 +377,9 @@ struct fx_engine {
     int64_t train_threads = 0;  // fx_train_fit: threads per forward+backward workgroup (256 / 512 / 1024; 0 = 1024)
     int num_cus = 256;
     int max_lds = 160 * 1024;
-    // layout of the score matrix the next launch writes: 0 = row-major (N, M) as the ABI hands it out (np.stack axis=1);
-    // > 0 = member-major planes `planar_stride` floats apart (the engine's own intermediate when only the mean is wanted:
-    // a unit's 16 scores are then one contiguous 64-byte store instead of 16 four-byte stores 4*M bytes apart)
-    int64_t planar_stride = 0;
-    // fused ensemble mean: set by the host / device entry points around score_dispatch when only the mean is wanted; a launcher
-    // that averages in-kernel (small launches of the canonical CNN: score_cnn_quad.hip) sets fused_mean_done
-    float* fuse_mean_out = nullptr;     // (explorer-size form: option fuse_mean)
-    float* fuse_mean_batch_out = nullptr;   // (batch form: option fuse_mean_batch)
-    float* score_table_mean_out = nullptr;  // (the lookup form, score_cnn_lookup.hip: a thread there holds a row's M scores, so the mean costs it one more store)
+    // (read: option "fused_mean_done") the last score + mean call: its scoring kernel wrote the mean (FxOutcome::mean_done), no mean launch
+    // followed.  Kept on the engine because fx_engine_get_option reads it long after the call; score_then_mean writes it once, from
+    // its dispatch's outcome, and nothing reads it to decide anything
     bool fused_mean_done = false;
     // resident small-call form (score_cnn_quad.hip / score_dense_small.hip, SERVER): one workgroup per (member, tile slot) stays
     // on the device between explorer-size calls and answers them through the mailboxes above
@@ -399,20 +432,15 @@ struct fx_engine {
     int64_t fuse_mean_batch = 0; // A/B build: 1 = batch launches of the 4-letter CNN (rows resident in device memory, mean-only calls) let the LAST member to finish a tile average it in the
                                 // scoring kernel (written-through scores, one relaxed device-scope ticket per tile, no fences) instead of launching the mean kernel.  Bit-identical, SLOWER: 183.5 -> 185.1 us per headline step (profiles/r6_fused_mean_ab.log)
     int64_t fuse_mean = 0;      // 1 = explorer-size CNN ensemble calls average in the scoring kernel (last member to finish a tile, tickets + device-scope fences) instead of launching the mean kernel.  Bit-identical, but the two fences cost what the 3 us launch saves: 32.1 vs 32.2 us per call (profiles/r3_fused_mean_ab.log): off, kept as the A/B
-    // launched-first host call (fx_score_begin_staged): what the launchers that can wait for rows copy into their arguments, and
-    // whether the launch just enqueued did (a launcher that cannot returns FX_EUNSUPPORTED before it enqueues anything)
-    struct { bool on = false, used = false; FxRowsReady r = {nullptr, 0, 0, 0, 0}; FxRelay relay = {nullptr, nullptr, 0, 0, 0}; bool relay_used = false; } rows_req;
     int64_t dense_prefetch = 1; // MLP / GE launches that read rows from host memory ask for the next tile's bytes a tile ahead: 1 = in a relay of >= 4 members (where it pays), 2 = always (A/B), 0 = never
     int64_t relay_spread = 0;   // 1 = relay launches take their unit ranges in plain block order: member 0's workgroups on all eight XCDs instead of one (no gain: A/B)
     unsigned* relay_flags = nullptr; size_t relay_flag_words = 0; unsigned relay_seq = 0;
     int64_t launch_relay = 1;   // 1 = launched-first calls of dense ensembles whose plan says "copy" relay the rows through member 0's workgroups (0 = such calls pack, upload, then launch: A/B)
     int64_t launch_relay_calls = 0;
-    int64_t rows_min_share = 0;                          // (request) tiles in the shortest per-SIMD share of the launch
     unsigned* rows_words = nullptr;                      // 16 lines of device memory the host stores into (large BAR), or null
     bool rows_refused = false;
     unsigned rows_base = 0;
-    bool ascii_host = false;    // (request) the launch about to be enqueued reads its sequences from pinned HOST memory (zero-copy host calls)
-    int64_t cnn_stage_host = 1; // 1 = such launches of the canonical 4-letter CNN copy a tile's bytes into LDS with one wide load (0 = a byte load per position: A/B; 2 = 1 + the next tile's bytes asked for a tile ahead: A/B, no gain)
+    int64_t cnn_stage_host = 1; // 1 = launches of the canonical 4-letter CNN that read their sequences from pinned host memory (FxRequest::host_rows) copy a tile's bytes into LDS with one wide load (0 = a byte load per position: A/B; 2 = 1 + the next tile's bytes asked for a tile ahead: A/B, no gain)
     int64_t launch_first_calls = 0, launch_first_redone = 0;   // (read) host calls launched before their strings were packed; of those, redone the plain way
     int64_t launch_first = 1;   // 1 = big list[str] calls whose kernels can wait for rows are launched before the strings are packed (0 = pack, then launch: A/B)
     // chunked host call in flight (fx_score_begin / _submit / _finish)
@@ -442,16 +470,6 @@ struct fx_engine {
     int64_t zero_copy_bytes = 256 << 10;   // host calls whose input + output are at most this many bytes run zero-copy: the kernels read the sequences from / write the scores to mapped pinned host memory
     int64_t zero_copy_mode = -1;           // host calls beyond zero_copy_bytes: -1 = zero-copy when the plan (fx_plan_host_call) says the PCIe reads hide behind the kernels, 0 = always copy, 1 = always zero-copy (A/B)
 };
-
-// The launcher's part of a launched-first call's plan: as many stages as the shortest per-SIMD share has tiles.  false = too few
-// to order (nothing launched).
-inline bool fx_rows_plan(fx_engine* e) {
-    int64_t Q = e->rows_min_share;
-    if (Q > 2048) Q = 2048;
-    if (Q < 2) return false;
-    e->rows_req.r.Q = (int)Q;
-    return true;
-}
 
 struct fx_model {
     fx_engine* eng = nullptr;
@@ -571,11 +589,12 @@ __device__ __forceinline__ void fx_rows_wait(const FxRowsReady& r, int stage, in
 
 // ---------------------------------------------------------------- kernel launchers
 // (defined in the .hip files; all enqueue on e->stream and return an fx_status)
+// (the scoring launchers: a launch group -- M members, m_off of Mtot --, the rows, the scores' destination, the dispatch's request and outcome)
 int fx_launch_score_generic(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                            int64_t N, float* d_out_NM, int Mtot, int m_off);
+                            int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 // returns FX_EUNSUPPORTED if no MFMA instantiation matches (caller falls back to generic)
 int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                             int64_t N, float* d_out_NM, int Mtot, int m_off);
+                             int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 // conv1's outputs for all 4^5 windows of a member whose layout has the table (FxPackLayout::off_c1tab), from the packed image already in
 // m->d_packed; a no-op for every other model.  fx_model_set_weights calls it: every path that changes weights goes through there
 int fx_build_conv1_table(fx_engine* e, fx_model* m);
@@ -585,23 +604,23 @@ int fx_build_conv2_prefix(fx_engine* e, fx_model* m);
 // the head-only form of a launch group of canonical seq_len = 8 members (score_cnn_pooled.hip): builds the stale members' tables first when
 // `build`; FX_EUNSUPPORTED (nothing enqueued for the scores) when a table could not be allocated: the caller launches its conv form
 int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
-                               bool build);
+                               const FxRequest& rq, FxOutcome& out, bool build);
 // the members' score tables brought up to date on e->stream (score_cnn_pooled.hip): stale pooled-feature tables are built first when `build_pool`;
 // FX_EUNSUPPORTED when a table is stale and may not be built, or could not be allocated
-int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, bool build_pool);
+int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, const FxRequest& rq, bool build_pool);
 // the lookup form of such a launch group (score_cnn_lookup.hip): one table read per row and member, and the ensemble mean where score_then_mean
 // offers its destination and the group is the whole ensemble.  FX_EUNSUPPORTED (nothing enqueued for the scores) when a table could not be had:
 // the caller goes on with the head-only form
 int fx_launch_score_cnn_lookup(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
-                               bool build);
+                               const FxRequest& rq, FxOutcome& out, bool build);
 // the conv part of the two-kernel path alone, one 4-letter member: tile-major pooled features into d_pool (score_cnn_split.hip; test hook)
 int fx_launch_cnn_conv_only(fx_engine* e, fx_model* model, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_cnn_pair_conv(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, void* d_pool);
 int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                              int64_t N, float* d_out_NM, int Mtot, int m_off);
+                              int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 // small launches of the canonical 4-letter CNN, L <= 16 (TF-binding, RNA 14): one tile shared by a wave quad (score_cnn_quad.hip)
 int fx_launch_score_cnn_quad(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                             float* d_out_NM, int Mtot, int m_off);
+                             float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 // the resident form: one workgroup per model on `stream`, answering `d_mail`; *cap = sequences per request it serves.
 // FX_EUNSUPPORTED when the shape has no resident instantiation.
 // tell a resident generation to leave (its workgroups poll the flag between requests); the next eligible calls start a new one
@@ -695,15 +714,15 @@ __device__ __forceinline__ unsigned long long fx_server_wait(const FxMailIn* in,
 }
 #endif
 int fx_launch_score_cnn_pair(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                             int64_t N, float* d_out_NM, int Mtot, int m_off);
+                             int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 // small launches of the MLP: a tile's output tiles dealt to the waves of a workgroup (score_dense_small.hip)
 int fx_launch_score_mlp_small(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                              float* d_out_NM, int Mtot, int m_off);
+                              float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 int fx_mlp_first_layer_form(fx_engine* e, const FxShape& s, const FxPackLayout& lay);
 // MLP whose first-layer rows do not fit LDS beside the rest of the image and that takes its first layer position-major at batch size (option mlp_l1_pos, score_dense_l1.h)
 bool fx_mlp_l1_pos_applies(const fx_engine* e, const FxShape& s, const FxPackLayout& lay);
 int fx_launch_score_dense_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                               int64_t N, float* d_out_NM, int Mtot, int m_off);
+                               int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out);
 int fx_launch_mfma_probe(fx_engine* e, const float* d_a, const float* d_b, const float* d_c, float* d_d);
 int fx_launch_encode_onehot(fx_engine* e, const uint8_t* d_ascii, int64_t N, int L, int A, float* d_out);
 int fx_launch_ensemble_mean_planar(fx_engine* e, const float* d_planes, int64_t N, int M, int64_t stride, float* d_out32);

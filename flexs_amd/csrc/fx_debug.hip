@@ -104,14 +104,15 @@ int fx_debug_pack_layout(int kind, int L, int A, int F, int H, int K, int64_t* o
 }
 // Host only: the form of the fused CNN kernel (path 0: score_cnn_mfma.hip; 1: the conv part of score_cnn_split.hip) and the launch geometry that a
 // launch of M members of CNN(F, H, K) on N sequences would get from an engine with these properties and option overrides -- the launchers' own
-// pure functions (score_cnn_forms.h) on a default engine that never sees a device.  out24 = the sixteen form fields in the order of
+// pure functions (score_cnn_forms.h) on a default engine that never sees a device and the request that `rows_on` / `ascii_host` spell out.  out24 = the sixteen form fields in the order of
 // fx_cnn_form_fields, TG, seg_sb, LDS bytes, CnnFormId, pair_first, 1 in the A/B build.  Returns the status the launcher would return after
 // score_cnn_quad.hip / score_cnn_pair.hip declined (its message, if any, in msg), or the status fx_engine_set_option has for an override.
 int fx_debug_cnn_form_pick(int path, int L, int A, int F, int H, int K, int64_t N, int M, int num_cus, int max_lds, int rows_on, int ascii_host,
                            const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out24, char* msg, int msg_cap) {
     if (!out24 || path < 0 || path > 1 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
     fx_engine eng;
-    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    eng.num_cus = num_cus; eng.max_lds = max_lds;
+    FxRequest rq; rq.rows_on = rows_on != 0; rq.host_rows = ascii_host != 0;
     std::memset(out24, 0, 24 * sizeof(int64_t));
     if (msg && msg_cap > 0) msg[0] = 0;
     auto say = [&](const char* text) { if (msg && msg_cap > 0 && text) std::snprintf(msg, (size_t)msg_cap, "%s", text); };
@@ -122,7 +123,7 @@ int fx_debug_cnn_form_pick(int path, int L, int A, int F, int H, int K, int64_t 
     }
     const FxShape s{FX_CNN, L, A, F, H, K};
     const FxPackLayout lay = fx_pack_layout(s);
-    const CnnPick pk = path == 0 ? fx_cnn_pick_fused(&eng, s, lay, N, M) : fx_cnn_pick_conv(&eng, s, lay, N, M);
+    const CnnPick pk = path == 0 ? fx_cnn_pick_fused(&eng, rq, s, lay, N, M) : fx_cnn_pick_conv(&eng, rq, s, lay, N, M);
     out24[16] = pk.TG; out24[17] = pk.seg_sb; out24[18] = (int64_t)pk.lds; out24[19] = pk.id; out24[20] = pk.pair_first;
 #if defined(FX_AB)
     out24[21] = 1;
@@ -139,7 +140,8 @@ int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, 
                            const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out4) {
     if (!out4 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
     fx_engine eng;
-    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    eng.num_cus = num_cus; eng.max_lds = max_lds;
+    FxRequest rq; rq.rows_on = rows_on != 0; rq.host_rows = ascii_host != 0;
     std::memset(out4, 0, 4 * sizeof(int64_t));
     for (int i = 0; i < n_opts; ++i) {
         int64_t* slot = nullptr;
@@ -149,9 +151,9 @@ int fx_debug_cnn_pool_pick(int L, int A, int F, int H, int K, int64_t N, int M, 
     const FxShape s{FX_CNN, L, A, F, H, K};
     const FxPackLayout lay = fx_pack_layout(s);
     out4[2] = lay.off_c1tab >= 0;
-    if (int rc = fx_cnn_fused_supported(&eng, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
-    const CnnPick pk = fx_cnn_pick_fused(&eng, s, lay, N, M);
-    out4[0] = fx_cnn_pool_decide(&eng, lay, pk, N, fresh != 0);
+    if (int rc = fx_cnn_fused_supported(&eng, rq, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
+    const CnnPick pk = fx_cnn_pick_fused(&eng, rq, s, lay, N, M);
+    out4[0] = fx_cnn_pool_decide(&eng, rq, lay, pk, N, fresh != 0);
     out4[1] = pk.id; out4[3] = pk.rc;
     return FX_OK;
 }
@@ -161,7 +163,8 @@ int fx_debug_cnn_score_pick(int L, int A, int F, int H, int K, int64_t N, int M,
                             const char* const* opt_keys, const int64_t* opt_values, int n_opts, int64_t* out4) {
     if (!out4 || N < 1 || M < 1 || n_opts < 0 || (n_opts && (!opt_keys || !opt_values))) return FX_EINVAL;
     fx_engine eng;
-    eng.num_cus = num_cus; eng.max_lds = max_lds; eng.rows_req.on = rows_on != 0; eng.ascii_host = ascii_host != 0;
+    eng.num_cus = num_cus; eng.max_lds = max_lds;
+    FxRequest rq; rq.rows_on = rows_on != 0; rq.host_rows = ascii_host != 0;
     std::memset(out4, 0, 4 * sizeof(int64_t));
     for (int i = 0; i < n_opts; ++i) {
         int64_t* slot = nullptr;
@@ -170,9 +173,9 @@ int fx_debug_cnn_score_pick(int L, int A, int F, int H, int K, int64_t N, int M,
     }
     const FxShape s{FX_CNN, L, A, F, H, K};
     const FxPackLayout lay = fx_pack_layout(s);
-    if (int rc = fx_cnn_fused_supported(&eng, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
-    const CnnPick pk = fx_cnn_pick_fused(&eng, s, lay, N, M);
-    const CnnPoolDecision pool = fx_cnn_pool_decide(&eng, lay, pk, N, fresh != 0);
+    if (int rc = fx_cnn_fused_supported(&eng, rq, s, lay, M)) { out4[3] = rc; return FX_OK; }   // (the two-kernel path: no table form)
+    const CnnPick pk = fx_cnn_pick_fused(&eng, rq, s, lay, N, M);
+    const CnnPoolDecision pool = fx_cnn_pool_decide(&eng, rq, lay, pk, N, fresh != 0);
     out4[0] = fx_cnn_score_decide(&eng, pool);
     out4[1] = pool; out4[2] = pk.id; out4[3] = pk.rc;
     return FX_OK;

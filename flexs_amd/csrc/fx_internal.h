@@ -6,6 +6,10 @@
 //   fx_nam.hip       NoisyAbstractModel: distances, device cache, table landscapes, blend
 //   fx_debug.hip     test / profiling hooks
 // no behaviour change: the kernels are other translation units and did not move).  Nothing here is part of the ABI; hidden visibility.
+// A dispatch is (engine, members, rows, request) -> outcome: score_dispatch / score_then_mean take the FxRequest their caller built on
+// its own stack (fx_common.h: layout, host rows, mean destination, pre-launch, launched-first part) and fill an FxOutcome; the planner,
+// the launchers and the form choices read the request and nothing else about the call.  The engine holds device state and options,
+// nothing per call.
 #pragma once
 #include <cstdint>
 #include <cstddef>
@@ -33,9 +37,9 @@ FXI int server_call(fx_engine* e, fx_model* const* models, int M, const uint8_t*
 FXI int64_t server_since(const fx_engine* e);      // fx_resident.hip
 FXI void server_stop(fx_engine* e);      // fx_resident.hip
 FXI int wait_for_results(fx_engine* e, unsigned want_seq = 0);      // fx_resident.hip
-FXI int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L, float* d_NM, int64_t planar_stride = 0);      // fx_score.hip
+FXI int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_NM, const FxRequest& rq, FxOutcome& out);      // fx_score.hip
 FXI int validate_models(fx_engine* e, fx_model* const* models, int M, int L, const uint8_t* lut);      // fx_score.hip
-FXI int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L, float* d_planes, int64_t stride, float* mean_dst);      // fx_score.hip
+FXI int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_planes, float* mean_dst, const FxRequest& rq, FxOutcome& out);      // fx_score.hip: rq.stride > 0, rq.mean_out is its own to set
 FXI int fx_launch_error_word(fx_engine* e, float* d_dst);      // fx_engine.hip
 FXI void fx_steps_forget_model(fx_model* m);      // fx_step.hip: the prepared steps that hold `m` are dead from here on
 FXI void fx_steps_forget_engine(fx_engine* e);      // fx_step.hip: ... every prepared step of `e`

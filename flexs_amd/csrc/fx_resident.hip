@@ -275,11 +275,11 @@ extern "C" {
 // to the same pinned planes / matrix.  It fills its weights and waits for its request word.
 void lp_arm(fx_engine* e, fx_model* const* models, int M, int64_t N, int L, const uint8_t lut[256], float* out_dev, int64_t stride, int mode) {
     if (!e->lp_prelaunch || !e->done_flag || e->trace || !lp_mail_ensure(e)) return;
-    e->lp_arm_next = true;
-    const int rc = score_dispatch(e, models, M, e->lp_mail->bytes, N, L, out_dev, stride);
-    e->lp_arm_next = false;
+    FxRequest rq; FxOutcome out;                           // (host rows: the form choices see what they saw for the zero-copy host call this instance repeats)
+    rq.arm_next = true; rq.stride = stride; rq.host_rows = true;
+    const int rc = score_dispatch(e, models, M, e->lp_mail->bytes, N, out_dev, rq, out);
     e->done_armed = false;                                 // (nobody waits for this launch's flag until it has been asked)
-    if (rc != FX_OK || e->lp_launches != 1 || e->dispatch_groups != 1) {
+    if (rc != FX_OK || out.lp_launches != 1 || out.groups != 1) {
         // (not the layer-parallel form after all: whatever was enqueued scored the mailbox's old bytes into the scratch planes --
         //  harmless, and stream-ordered before anything that reads them)
         (void)hipGetLastError();

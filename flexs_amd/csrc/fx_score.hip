@@ -19,31 +19,19 @@ extern "C" {
 
 // ------------------------------------------------------------------ scoring
 
-// (for the launchers: the sequences of the launches enqueued while this lives are read from pinned host memory)
-struct HostBytes {
-    fx_engine* e;
-    explicit HostBytes(fx_engine* e_) : e(e_) { e->ascii_host = true; }
-    ~HostBytes() { e->ascii_host = false; }
-};
-
-// planar_stride == 0: d_NM is the row-major (N, M) matrix of the ABI; > 0: M member planes that far apart.
-int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L,
-                          float* d_NM, int64_t planar_stride) {
-    if (!e->lp_arm_next) lp_disarm(e);                     // (a pre-launched instance of another call shape holds the CUs: it leaves)
-    e->lp_launches = 0;
-    e->dispatch_groups = 0;
+// One dispatch: (engine, members, rows, request) -> outcome.  rq.stride == 0: d_NM is the row-major (N, M) matrix of the ABI; > 0: M member
+// planes that far apart.  Everything the caller wants from THIS dispatch is in `rq`, everything the launchers report about it in `out`.
+int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_NM,
+                   const FxRequest& rq, FxOutcome& out) {
+    out = FxOutcome{};
+    if (!rq.arm_next) lp_disarm(e);                        // (a pre-launched instance of another call shape holds the CUs: it leaves)
     // a launch whose workgroups would not all find a CU beside the resident ones tells those to leave (they hold most of their
     // CU's LDS: a persistent workgroup that has to wait for one of them would wait for their idle exit)
     if (e->server.running && (int64_t)M * ((N + 15) / 16) + e->server.wgs > e->num_cus) server_stop(e);
-    if (e->poison_outputs && !e->lp_arm_next)   // scores are nan_to_num'ed, so a NaN that survives is an element no kernel wrote
+    if (e->poison_outputs && !rq.arm_next)   // scores are nan_to_num'ed, so a NaN that survives is an element no kernel wrote
         // (not for a pre-launched instance: the memset would run between the end of the instance being answered and the host
         //  reading ITS results from the same pinned planes; lp_serve_armed poisons them on the host instead)
-        FX_HIP(e, hipMemsetAsync(d_NM, 0xFF, sizeof(float) * (planar_stride ? (size_t)planar_stride * (size_t)M : (size_t)N * (size_t)M), e->stream));
-    struct Layout {                                     // the launchers read the layout from the engine
-        fx_engine* e;
-        Layout(fx_engine* e_, int64_t s) : e(e_) { e->planar_stride = s; }
-        ~Layout() { e->planar_stride = 0; }
-    } layout(e, planar_stride);
+        FX_HIP(e, hipMemsetAsync(d_NM, 0xFF, sizeof(float) * (rq.stride ? (size_t)rq.stride * (size_t)M : (size_t)N * (size_t)M), e->stream));
     // group consecutive members into launches of <= FX_MAX_M homogeneous models
     for (int m0 = 0; m0 < M;) {
         int cnt = 1;
@@ -54,43 +42,38 @@ int score_dispatch(fx_engine* e, fx_model* const* models, int M, const uint8_t* 
             ++cnt;
         }
         int rc = FX_EUNSUPPORTED;
-        e->dispatch_groups += 1;
+        out.groups += 1;
         e->done_armed = false;                             // (only the LAST launch of a dispatch may offer the completion flag)
-        if (e->rows_req.on) {
+        if (rq.rows_on) {
             // launched-first host call: ONE launch of a kernel that waits for its rows, or nothing at all (the caller then packs first)
             if (cnt != M || e->force_generic) return FX_EUNSUPPORTED;
-            if (s0.kind == FX_CNN) return fx_launch_score_cnn_mfma(e, models, M, d_ascii, N, d_NM, M, 0);
-            return fx_launch_score_dense_mfma(e, models, M, d_ascii, N, d_NM, M, 0);
+            if (s0.kind == FX_CNN) return fx_launch_score_cnn_mfma(e, models, M, d_ascii, N, d_NM, M, 0, rq, out);
+            return fx_launch_score_dense_mfma(e, models, M, d_ascii, N, d_NM, M, 0, rq, out);
         }
         if (!e->force_generic) {
             if (s0.kind == FX_CNN) {
-                rc = fx_launch_score_cnn_mfma(e, models + m0, cnt, d_ascii, N, d_NM, M, m0);
-                if (rc == FX_EUNSUPPORTED) rc = fx_launch_score_cnn_split(e, models + m0, cnt, d_ascii, N, d_NM, M, m0);
+                rc = fx_launch_score_cnn_mfma(e, models + m0, cnt, d_ascii, N, d_NM, M, m0, rq, out);
+                if (rc == FX_EUNSUPPORTED) rc = fx_launch_score_cnn_split(e, models + m0, cnt, d_ascii, N, d_NM, M, m0, rq, out);
             }
-            else rc = fx_launch_score_dense_mfma(e, models + m0, cnt, d_ascii, N, d_NM, M, m0);
+            else rc = fx_launch_score_dense_mfma(e, models + m0, cnt, d_ascii, N, d_NM, M, m0, rq, out);
         }
-        if (rc == FX_EUNSUPPORTED) rc = fx_launch_score_generic(e, models + m0, cnt, d_ascii, N, d_NM, M, m0);
+        if (rc == FX_EUNSUPPORTED) rc = fx_launch_score_generic(e, models + m0, cnt, d_ascii, N, d_NM, M, m0, rq, out);
         if (rc) return rc;
         m0 += cnt;
     }
-    (void)L;
     return FX_OK;
 }
 
-// score into member-major planes, then the NumPy-order mean -- in the scoring kernel itself where a launcher offers it
-int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, int L,
-                    float* d_planes, int64_t stride, float* mean_dst) {
-    e->fuse_mean_out = (e->fuse_mean && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
-    e->fuse_mean_batch_out = (e->fuse_mean_batch && stride && M > 1 && M <= 16) ? mean_dst : nullptr;
-    e->score_table_mean_out = (stride && M > 1 && M <= 16) ? mean_dst : nullptr;
-    e->fused_mean_done = false;
-    const int rc = score_dispatch(e, models, M, d_ascii, N, L, d_planes, stride);
-    e->fuse_mean_out = nullptr;
-    e->fuse_mean_batch_out = nullptr;
-    e->score_table_mean_out = nullptr;
+// score into member-major planes (rq_in.stride apart), then the NumPy-order mean -- in the scoring kernel itself where a launcher offers it
+int score_then_mean(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_planes, float* mean_dst,
+                    const FxRequest& rq_in, FxOutcome& out) {
+    FxRequest rq = rq_in;
+    rq.mean_out = (rq.stride && M > 1 && M <= 16) ? mean_dst : nullptr;
+    const int rc = score_dispatch(e, models, M, d_ascii, N, d_planes, rq, out);
+    e->fused_mean_done = out.mean_done;                    // (option "fused_mean_done": the last score + mean call)
     if (rc) return rc;
-    if (e->fused_mean_done) return FX_OK;
-    return fx_launch_ensemble_mean_planar(e, d_planes, N, M, stride, mean_dst);
+    if (out.mean_done) return FX_OK;
+    return fx_launch_ensemble_mean_planar(e, d_planes, N, M, rq.stride, mean_dst);
 }
 
 int validate_models(fx_engine* e, fx_model* const* models, int M, int L, const uint8_t* lut) {
@@ -119,6 +102,7 @@ int fx_score_dev(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_
     rc = fx_upload_lut(e, lut);
     if (rc) return rc;
     float* d_NM = d_out_NM;
+    FxRequest rq; FxOutcome out;                           // (device rows)
     if (!d_NM) {
         // only the mean is wanted: the intermediate is the engine's own, laid out member-major (contiguous stores)
         const int64_t stride = M <= 16 ? planar_stride_for(N) : 0;
@@ -126,9 +110,10 @@ int fx_score_dev(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_
         rc = fx_scratch(e, 1, sizeof(float) * (stride ? (size_t)stride * (size_t)M : (size_t)N * (size_t)M), &p);
         if (rc) return rc;
         d_NM = (float*)p;
-        if (stride) return score_then_mean(e, models, M, d_ascii, N, L, d_NM, stride, d_out_mean);
+        rq.stride = stride;
+        if (stride) return score_then_mean(e, models, M, d_ascii, N, d_NM, d_out_mean, rq, out);
     }
-    rc = score_dispatch(e, models, M, d_ascii, N, L, d_NM);
+    rc = score_dispatch(e, models, M, d_ascii, N, d_NM, rq, out);
     if (rc) return rc;
     if (d_out_mean) rc = fx_launch_ensemble_reduce(e, d_NM, N, M, nullptr, d_out_mean, nullptr);
     return rc;
@@ -146,7 +131,9 @@ int fx_score_planes_dev(fx_engine* e, fx_model* const* models, int M, const uint
     FX_HIP(e, hipSetDevice(e->device));
     if ((rc = fx_upload_lut(e, lut))) return rc;
     e->counters.device_calls += 1; e->counters.sequences += N; e->counters.forwards += N * M;
-    return score_dispatch(e, models, M, d_ascii, N, L, d_planes, stride);
+    FxRequest rq; FxOutcome out;                           // (device rows)
+    rq.stride = stride;
+    return score_dispatch(e, models, M, d_ascii, N, d_planes, rq, out);
 }
 
 int fx_ensemble_mean_planes_dev(fx_engine* e, const float* d_planes, int64_t N, int M, int64_t stride, float* d_out_mean) {
@@ -171,7 +158,9 @@ int fx_score_mean_planes_dev(fx_engine* e, fx_model* const* models, int M, const
     FX_HIP(e, hipSetDevice(e->device));
     if ((rc = fx_upload_lut(e, lut))) return rc;
     e->counters.device_calls += 1; e->counters.sequences += N; e->counters.forwards += N * M;
-    return score_then_mean(e, models, M, d_ascii, N, L, d_planes, stride, d_out_mean);
+    FxRequest rq; FxOutcome out;                           // (device rows)
+    rq.stride = stride;
+    return score_then_mean(e, models, M, d_ascii, N, d_planes, d_out_mean, rq, out);
 }
 
 int fx_staging_input(fx_engine* e, int64_t bytes, void** host) {
@@ -288,16 +277,17 @@ int fx_score(fx_engine* e, fx_model* const* models, int M, const uint8_t* ascii,
         FX_HIP(e, hipHostGetDevicePointer(&dm_out, h_out, 0));
         float* m_NM = (float*)dm_out;
         float* m_mean = (float*)((char*)dm_out + nm_bytes);
-        HostBytes host_bytes(e);
+        FxRequest rq; FxOutcome out;                       // (the kernels read the pinned staging area)
+        rq.host_rows = true; rq.stride = stride;
         if (host_mean) {
             e->call_prof_ns[0] = server_since(e);
             // a pre-launched instance of exactly this call (the caller is back within the idle window): no launch, no weight fill
             bool served = lp_armed_matches(e, models, M, N, L, lut, stride, 1, m_NM) && lp_serve_armed(e, models, M, ascii, N, L, lut, m_NM, stride, 1, h_out, inter_bytes);
             if (!served) {
-                if ((rc = score_dispatch(e, models, M, (const uint8_t*)dm_in, N, L, m_NM, stride))) return rc;
+                if ((rc = score_dispatch(e, models, M, (const uint8_t*)dm_in, N, m_NM, rq, out))) return rc;
                 e->call_prof_ns[1] = server_since(e);
                 // answered by the layer-parallel form alone: its NEXT instance is enqueued now, beside this one's work
-                const bool lp = e->done_armed && e->lp_launches == 1 && e->dispatch_groups == 1;
+                const bool lp = e->done_armed && out.lp_launches == 1 && out.groups == 1;
                 const unsigned seq = lp ? e->done_seq : 0;
                 if (lp) lp_arm(e, models, M, N, L, lut, m_NM, stride, 1);
                 if ((rc = wait_for_results(e, seq))) return rc;
@@ -308,7 +298,7 @@ int fx_score(fx_engine* e, fx_model* const* models, int M, const uint8_t* ascii,
             e->call_prof_ns[3] = server_since(e);
             return FX_OK;
         } else if (stride) {
-            if ((rc = score_then_mean(e, models, M, (const uint8_t*)dm_in, N, L, d_NM, stride, m_mean))) return rc;
+            if ((rc = score_then_mean(e, models, M, (const uint8_t*)dm_in, N, d_NM, m_mean, rq, out))) return rc;
             e->done_armed = false;                         // (the mean kernel, or a fused mean, is the last writer)
         } else {
             const bool plain_matrix = out_NM && !out_mean && N <= e->host_mean_below;
@@ -316,13 +306,13 @@ int fx_score(fx_engine* e, fx_model* const* models, int M, const uint8_t* ascii,
             unsigned seq = 0;
             e->call_prof_ns[0] = server_since(e);
             if (!served) {
-                if ((rc = score_dispatch(e, models, M, (const uint8_t*)dm_in, N, L, out_NM ? m_NM : d_NM, stride))) return rc;
+                if ((rc = score_dispatch(e, models, M, (const uint8_t*)dm_in, N, out_NM ? m_NM : d_NM, rq, out))) return rc;
                 e->call_prof_ns[1] = server_since(e);
                 if (out_mean) {
                     if ((rc = fx_launch_ensemble_reduce(e, out_NM ? m_NM : d_NM, N, M, nullptr, m_mean, nullptr))) return rc;
                     e->done_armed = false;
                 }
-                if (plain_matrix && e->done_armed && e->lp_launches == 1 && e->dispatch_groups == 1) {
+                if (plain_matrix && e->done_armed && out.lp_launches == 1 && out.groups == 1) {
                     seq = e->done_seq;
                     lp_arm(e, models, M, N, L, lut, m_NM, 0, 2);
                 }
@@ -371,8 +361,10 @@ int fx_score(fx_engine* e, fx_model* const* models, int M, const uint8_t* ascii,
         e->counters.bytes_h2d += (int64_t)in_bytes;
         e->counters.bytes_d2h += (int64_t)((out_mean ? mean_bytes : 0) + (out_NM ? nm_bytes : 0));
         FX_HIP(e, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, e->stream));
-        if (stride) rc = score_then_mean(e, models, M, (const uint8_t*)d_in, N, L, d_NM, stride, d_mean);
-        else rc = score_dispatch(e, models, M, (const uint8_t*)d_in, N, L, d_NM, stride);
+        FxRequest rq; FxOutcome out;                       // (the rows were uploaded: device rows)
+        rq.stride = stride;
+        if (stride) rc = score_then_mean(e, models, M, (const uint8_t*)d_in, N, d_NM, d_mean, rq, out);
+        else rc = score_dispatch(e, models, M, (const uint8_t*)d_in, N, d_NM, rq, out);
         if (rc) return rc;
         if (out_mean) {
             if (!stride && (rc = fx_launch_ensemble_reduce(e, d_NM, N, M, nullptr, d_mean, nullptr))) return rc;
@@ -460,21 +452,19 @@ static int staged_enqueue(fx_engine* e, bool* waits) {
     int64_t G = e->grid_blocks > 0 ? e->grid_blocks : e->num_cus;
     if (G > U) G = U;
     const int64_t nb = M > 1 ? (G + M - 1) / M : G;      // workgroups of one member, at most
-    e->rows_min_share = TG / (nb > 0 ? nb : 1) / 4;
-    e->rows_req.on = true; e->rows_req.used = false; e->rows_req.relay_used = false;
-    e->rows_req.r = FxRowsReady{c.words, c.base, c.lanes, 0, c.pitch};
-    e->rows_req.relay = c.relay ? FxRelay{c.d_in, e->relay_flags, e->relay_seq, (16 * c.L + 127) / 128 * 128, (int)e->relay_spread} : FxRelay{nullptr, nullptr, 0, 0, 0};
-    HostBytes host_bytes(e);
+    FxRequest rq; FxOutcome out;                           // (host rows that arrive while the kernels run)
+    rq.host_rows = true; rq.stride = c.stride; rq.rows_on = true;
+    rq.min_share = TG / (nb > 0 ? nb : 1) / 4;
+    rq.rows = FxRowsReady{c.words, c.base, c.lanes, 0, c.pitch};
+    if (c.relay) rq.relay = FxRelay{c.d_in, e->relay_flags, e->relay_seq, (16 * c.L + 127) / 128 * 128, (int)e->relay_spread};
     int rc;
-    if (c.stride) rc = score_then_mean(e, c.models.data(), M, (const uint8_t*)dm_in, c.N, c.L, c.d_nm, c.stride, m_mean);
+    if (c.stride) rc = score_then_mean(e, c.models.data(), M, (const uint8_t*)dm_in, c.N, c.d_nm, m_mean, rq, out);
     else {
-        rc = score_dispatch(e, c.models.data(), M, (const uint8_t*)dm_in, c.N, c.L, c.want_nm ? m_NM : c.d_nm, 0);
+        rc = score_dispatch(e, c.models.data(), M, (const uint8_t*)dm_in, c.N, c.want_nm ? m_NM : c.d_nm, rq, out);
         if (!rc && c.want_mean) rc = fx_launch_ensemble_reduce(e, c.want_nm ? m_NM : c.d_nm, c.N, M, nullptr, m_mean, nullptr);
     }
-    *waits = e->rows_req.used;
-    e->rows_req.on = false;
-    e->rows_req.relay = FxRelay{nullptr, nullptr, 0, 0, 0};
-    c.Q = e->rows_req.r.Q;
+    *waits = out.rows_used;
+    c.Q = out.Q;
     e->done_armed = false;                                 // (finish waits on the stream: the mean kernel may be the last writer)
     return rc;
 }
@@ -636,8 +626,9 @@ int fx_score_submit(fx_engine* e, int64_t row0, int64_t rows) {
         float* m_nm = (float*)dm_out + row0 * M;
         float* m_mean = (float*)((char*)dm_out + nm_bytes) + row0;
         float* nm = c.want_nm ? m_nm : c.d_nm + row0 * M;
-        HostBytes host_bytes(e);
-        if ((rc = score_dispatch(e, c.models.data(), M, (const uint8_t*)dm_in + row0 * c.L, rows, c.L, nm))) return rc;
+        FxRequest rq; FxOutcome out;                       // (the piece's kernels read the pinned staging area)
+        rq.host_rows = true;
+        if ((rc = score_dispatch(e, c.models.data(), M, (const uint8_t*)dm_in + row0 * c.L, rows, nm, rq, out))) return rc;
         if (c.want_mean && (rc = fx_launch_ensemble_reduce(e, nm, rows, M, nullptr, m_mean, nullptr))) return rc;
         const int k = c.pieces;
         // "piece k is done": a word written by the command processor behind the piece's launches and polled in pinned host
@@ -667,7 +658,8 @@ int fx_score_submit(fx_engine* e, int64_t row0, int64_t rows) {
         FX_HIP(e, hipStreamWaitEvent(e->stream, e->ev_in[k], 0));
     }
     float* nm = c.d_nm + row0 * M;
-    if ((rc = score_dispatch(e, c.models.data(), M, c.d_in + row0 * c.L, rows, c.L, nm))) return rc;
+    FxOutcome out;
+    if ((rc = score_dispatch(e, c.models.data(), M, c.d_in + row0 * c.L, rows, nm, FxRequest{}, out))) return rc;   // (the piece was uploaded: device rows)
     if (c.want_mean)
         if ((rc = fx_launch_ensemble_reduce(e, nm, rows, M, nullptr, c.d_mean + row0, nullptr))) return rc;
     if (two) {

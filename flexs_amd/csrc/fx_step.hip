@@ -90,8 +90,10 @@ int fx_step_launch(fx_step* s, const uint8_t* d_ascii, int64_t N) {
             s->lut_seen = true;
         }
         e->counters.device_calls += 1; e->counters.sequences += N; e->counters.forwards += N * M;
-        rc = s->d_mean ? score_then_mean(e, s->models.data(), M, d_ascii, N, s->L, s->d_planes, s->stride, s->d_mean)
-                       : score_dispatch(e, s->models.data(), M, d_ascii, N, s->L, s->d_planes, s->stride);
+        FxRequest rq; FxOutcome out;                       // (device rows)
+        rq.stride = s->stride;
+        rc = s->d_mean ? score_then_mean(e, s->models.data(), M, d_ascii, N, s->d_planes, s->d_mean, rq, out)
+                       : score_dispatch(e, s->models.data(), M, d_ascii, N, s->d_planes, rq, out);
         if (rc) return rc;
     }
     return s->d_err_word ? fx_launch_error_word(e, s->d_err_word) : FX_OK;

@@ -115,22 +115,22 @@ inline bool fx_cnn_segmented(const fx_engine* e, int64_t U, int L1, int min_l1, 
 
 // ---------------------------------------------------------------- fused kernel (score_cnn_mfma.hip)
 // The shapes the fused kernel covers at all; checked before score_cnn_quad.hip is tried.
-inline int fx_cnn_fused_supported(const fx_engine* e, const FxShape& s, const FxPackLayout& lay, int M) {
+inline int fx_cnn_fused_supported(const fx_engine* e, const FxRequest& rq, const FxShape& s, const FxPackLayout& lay, int M) {
     // num_filters 17..32 (two channel tiles; missing channels are zero padding of the packed blocks); kernel_size 5
     // everywhere, 3 and 7 for the canonical hidden width (97..112 units); everything else -> shape-agnostic kernels
     if ((lay.FT != 2 && !(lay.FT == 1 && s.K == 5 && lay.HT == 7)) || (s.A != 4 && s.A != 20 && s.A != 2)) return FX_EUNSUPPORTED;
     if (s.K != 5 && !((s.K == 3 || s.K == 7) && lay.HT == 7)) return FX_EUNSUPPORTED;
     if (M > FX_MAX_M) return FX_EINVAL;
     // a launched-first host call (rows arrive while the kernel runs): the whole-tile-per-wave forms of the 4-letter CNN only
-    if (e->rows_req.on && !(s.A == 4 && s.K == 5 && lay.FT == 2)) return FX_EUNSUPPORTED;
+    if (rq.rows_on && !(s.A == 4 && s.K == 5 && lay.FT == 2)) return FX_EUNSUPPORTED;
     return FX_OK;
 }
 
-inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxShape& s, const FxPackLayout& lay, int64_t N, int M) {
+inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxRequest& rq, const FxShape& s, const FxPackLayout& lay, int64_t N, int M) {
     CnnPick pk;
     auto fail = [&](int rc, const char* msg = nullptr) { pk.rc = rc; pk.msg = msg; pk.id = CNN_NO_FORM; return pk; };
     auto form = [&](CnnFormId id, size_t lds) { pk.id = id; pk.lds = lds; return pk; };
-    if (int rc = fx_cnn_fused_supported(e, s, lay, M)) return fail(rc);
+    if (int rc = fx_cnn_fused_supported(e, rq, s, lay, M)) return fail(rc);
     const size_t max_lds = (size_t)e->max_lds;
     const size_t full = (size_t)lay.total_floats * 4 + 256 + 48, conv_only = (size_t)lay.conv_floats * 4 + 256 + 48;
     pk.TG = (N + 15) / 16;
@@ -177,7 +177,7 @@ inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxShape& s, const FxP
     // workgroups for the dense head.
     const int HT = lay.HT;
     // more than 128 hidden units at batch size: the two-kernel path, whose head streams the H x H layer through LDS slabs (score_cnn_split.hip)
-    if (HT >= 13 && e->cnn_head_slab && !e->rows_req.on && fx_cnn_units_per_cu(e, U, 16)) return fail(FX_EUNSUPPORTED);
+    if (HT >= 13 && e->cnn_head_slab && !rq.rows_on && fx_cnn_units_per_cu(e, U, 16)) return fail(FX_EUNSUPPORTED);
     if (HT != 1 && HT != 2 && HT != 4 && HT != 7 && HT != 8 && HT != 13 && HT != 16) return fail(FX_EUNSUPPORTED);
     int variant = (int)e->cnn_variant;
     const bool dl = full <= max_lds;                     // whole member in LDS, else dense head streams from L2
@@ -187,7 +187,7 @@ inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxShape& s, const FxP
     if (HT == 7) {
         // the sequences lie in host memory (zero-copy host calls): the forms that copy a tile's bytes into LDS first (STG) -- same
         // walk, same bits -- where the scratch fits beside the weights (explorer-size launches keep their own forms below)
-        if (e->ascii_host && e->cnn_stage_host && dl && (variant == 0 || variant == 7 || variant == 10 || variant == 11) &&
+        if (rq.host_rows && e->cnn_stage_host && dl && (variant == 0 || variant == 7 || variant == 10 || variant == 11) &&
             lds + 16 * ((16 * (size_t)s.L + 15) / 16 * 16) <= max_lds && !fx_cnn_small(e, U)) {
             pk.stg = true;
             if (big) return form(s.L == 8 ? CNN_UNROLLED8_W16 : s.L == 14 ? CNN_UNROLLED14_W16 : CNN_GENERIC_W16, lds);
@@ -222,13 +222,13 @@ inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxShape& s, const FxP
                     if (s.L != 8) return fail(FX_EINVAL, "cnn_variant 7 is a seq_len = 8 specialisation");
                     // ... with conv1 read from the member's table of windows instead of gathered (cnn_conv1_table = 0: A/B); not when the
                     // rows arrive while the kernel runs (the table's second round trip would stand behind the wait for the rows)
-                    pk.c1t = e->cnn_conv1_table && !e->rows_req.on && lay.off_c1tab >= 0;
+                    pk.c1t = e->cnn_conv1_table && !rq.rows_on && lay.off_c1tab >= 0;
                     // ... and conv2's first one or two taps per position read from the member's prefix tables (cnn_conv2_prefix; a form of
                     // the table form: every other launch silently runs all taps)
                     if (pk.c1t && e->cnn_conv2_prefix >= 1 && e->cnn_conv2_prefix <= FX_C2P_MAX_DEPTH && lay.off_c2p[e->cnn_conv2_prefix - 1] >= 0)
                         pk.c2p = (int)e->cnn_conv2_prefix;
                     // ... and the (tiles mod 4) last tiles of a workgroup walked by wave quads (round 6; cnn_quad_tail = 0: A/B)
-                    pk.qt = e->cnn_quad_tail && !e->rows_req.on && lds + (size_t)3 * 2 * 8 * 1024 <= max_lds;
+                    pk.qt = e->cnn_quad_tail && !rq.rows_on && lds + (size_t)3 * 2 * 8 * 1024 <= max_lds;
                     return form(CNN_UNROLLED8_W16, lds);
                 case 11:                                 // unrolled L = 8 form in 8-wave workgroups (256-register budget): small launches
                     if (s.L != 8) return fail(FX_EINVAL, "cnn_variant 11 is a seq_len = 8 specialisation");
@@ -243,7 +243,7 @@ inline CnnPick fx_cnn_pick_fused(const fx_engine* e, const FxShape& s, const FxP
     //  sequences take the quad form)
     const bool may_spread = HT == 7 && dl && e->cnn_seg < 0 && e->cnn_seg_multi;
     const bool multi = may_spread && 2 * U <= e->num_cus;
-    if (!e->rows_req.on && variant == 0 && !e->cnn_conv1_mfma && fx_cnn_segmented(e, U, L1, multi ? 13 : 24, lds, 2)) {
+    if (!rq.rows_on && variant == 0 && !e->cnn_conv1_mfma && fx_cnn_segmented(e, U, L1, multi ? 13 : 24, lds, 2)) {
         // Long sequences: cut the positions over several workgroups as well (halo: 3 positions per side).  As many
         // segments (>= 2 positions) as one wave of the grid holds, from 4-wave workgroups -- one wave per SIMD -- when
         // that gives as many as 8-wave ones would (score_cnn_pair.hip has the measurements behind both rules).
@@ -349,9 +349,9 @@ enum CnnPoolDecision : int {
 // `pk` is the launch's pick and is launched unchanged when the answer is CNN_POOL_NO.  The table form stands in for the 16-wave unrolled form
 // only, with the rows in device memory when the kernel starts.  A stale table is built when the launch is longer than the enumeration (MORE
 // than 4^8 rows per member: building is then no more conv work than the launch would do itself), or whatever its size with cnn_pool_table = 2.
-inline CnnPoolDecision fx_cnn_pool_decide(const fx_engine* e, const FxPackLayout& lay, const CnnPick& pk, int64_t N, bool all_fresh) {
+inline CnnPoolDecision fx_cnn_pool_decide(const fx_engine* e, const FxRequest& rq, const FxPackLayout& lay, const CnnPick& pk, int64_t N, bool all_fresh) {
     if (e->cnn_pool_table <= 0 || lay.off_c1tab < 0) return CNN_POOL_NO;
-    if (pk.rc || pk.id != CNN_UNROLLED8_W16 || pk.stg || e->rows_req.on || e->ascii_host) return CNN_POOL_NO;
+    if (pk.rc || pk.id != CNN_UNROLLED8_W16 || pk.stg || rq.rows_on || rq.host_rows) return CNN_POOL_NO;
     if (all_fresh) return CNN_POOL_USE;
     return (e->cnn_pool_table >= 2 || N > FX_POOL_ROWS) ? CNN_POOL_BUILD : CNN_POOL_NO;
 }
@@ -379,7 +379,7 @@ inline int fx_cnn_split_supported(const fx_engine* e, const FxShape& s, const Fx
 }
 
 // conv part only: one tile per wave, 8 waves, conv weights in LDS, first layer in gather form
-inline CnnPick fx_cnn_pick_conv(const fx_engine* e, const FxShape& s, const FxPackLayout& lay, int64_t N, int M) {
+inline CnnPick fx_cnn_pick_conv(const fx_engine* e, const FxRequest& rq, const FxShape& s, const FxPackLayout& lay, int64_t N, int M) {
     CnnPick pk;
     pk.rc = fx_cnn_split_supported(e, s, lay, M);
     pk.pair_first = s.A == 20;                           // protein alphabet: the conv part is the two-waves-per-tile kernel (score_cnn_pair.hip)
@@ -395,7 +395,7 @@ inline CnnPick fx_cnn_pick_conv(const fx_engine* e, const FxShape& s, const FxPa
     // tile's positions, as in the fused kernel -- bit-identical to the one-wave walk (K * 3 <= 16: the ring-window form)
     if (s.K * 3 <= 16 && fx_cnn_segmented(e, U, s.L - s.K + 1, 24, pk.lds, lay.FT)) pk.id = CNN_CONV_SEG;
     // batch launches (the wide-head path, round 6): four waves per SIMD, and the unrolled walk of the canonical short landscape
-    else if (s.K == 5 && lay.FT == 2 && fx_cnn_units_per_cu(e, U, 16) && !e->rows_req.on) pk.id = s.L == 8 ? CNN_CONV_UNROLLED8_W16 : CNN_CONV_W16;
+    else if (s.K == 5 && lay.FT == 2 && fx_cnn_units_per_cu(e, U, 16) && !rq.rows_on) pk.id = s.L == 8 ? CNN_CONV_UNROLLED8_W16 : CNN_CONV_W16;
     else pk.id = CNN_CONV_W8;
     return pk;
 }

@@ -750,7 +750,7 @@ __global__ void __launch_bounds__(Form::WAVES * 64) k_score_cnn_mfma(CnnArgs p) 
 }
 
 template <class Form>
-int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
+int launch_g(fx_engine* e, const FxRequest& rq, FxOutcome& out, const CnnArgs& a_in, size_t lds_bytes) {
     constexpr int FT = Form::FT, NT = Form::NT, WAVES = Form::WAVES, C2P = Form::C2P, waves = WAVES;
     constexpr bool SEG = Form::SEG, HEAD = Form::HEAD, STG = Form::STG, QT = Form::QT, C1T = Form::C1T;
     auto kern = k_score_cnn_mfma<Form>;
@@ -770,12 +770,12 @@ int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
 #endif
     a.stw_stride = STG ? (int)((16 * (size_t)a.L + 15) / 16 * 16) : 0;
     a.stw_ahead = ahead ? 1 : 0;
-    if (e->rows_req.on) {
+    if (rq.rows_on) {
         // (a launched-first call: this kernel waits for its rows tile by tile -- the forms that share a tile among waves do not)
-        if (SEG || NT != 1 || !HEAD || e->rows_req.relay.flags) return FX_EUNSUPPORTED;   // (no relay form of this kernel)
-        if (!fx_rows_plan(e)) return FX_EUNSUPPORTED;
-        a.ready = e->rows_req.r;
-        e->rows_req.used = true;
+        if (SEG || NT != 1 || !HEAD || rq.relay.flags) return FX_EUNSUPPORTED;   // (no relay form of this kernel)
+        if (!(out.Q = fx_rows_plan(rq.min_share))) return FX_EUNSUPPORTED;
+        a.ready = rq.rows; a.ready.Q = out.Q;
+        out.rows_used = true;
     }
     int64_t U = (int64_t)a.M * a.TG;
     int64_t blocks = e->grid_blocks > 0 ? e->grid_blocks : e->num_cus;
@@ -789,7 +789,7 @@ int launch_g(fx_engine* e, const CnnArgs& a_in, size_t lds_bytes) {
     if (C1T) e->counters.conv1_table_launches += 1;
     if (C2P > 0) e->counters.conv2_prefix_launches += 1;
 #if defined(FX_AB)
-    if (a.fm_mean) e->fused_mean_done = true;
+    if (a.fm_mean) out.mean_done = true;
 #endif
     return FX_OK;
 }

@@ -60,18 +60,18 @@ __global__ void __launch_bounds__(LOOKUP_THREADS) k_score_cnn_mfma_scoretab(Look
 }  // namespace
 
 int fx_launch_score_cnn_lookup(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
-                               bool build) {
+                               const FxRequest& rq, FxOutcome& out, bool build) {
     if (N == 0) return FX_OK;
     if (M < 1 || M > FX_MAX_M || models[0]->shape.L != 8) return FX_EUNSUPPORTED;
-    if (int rc = fx_cnn_score_tables(e, models, M, build)) return rc;
+    if (int rc = fx_cnn_score_tables(e, models, M, rq, build)) return rc;
     LookupArgs a{};
     a.ascii = d_ascii; a.lut = e->d_lut; a.out = d_out_NM; a.err = e->d_err;
     for (int m = 0; m < M; ++m) a.tab[m] = models[m]->d_scoretab;
     a.N = N; a.m_off = m_off;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     // the whole ensemble in this launch and a mean asked for (score_then_mean): the thread that has a row's scores averages them
-    const bool fuse = e->score_table_mean_out && e->planar_stride && m_off == 0 && M == Mtot && M > 1;
-    a.mean = fuse ? e->score_table_mean_out : nullptr;
+    const bool fuse = rq.mean_out && rq.stride && m_off == 0 && M == Mtot && M > 1;
+    a.mean = fuse ? rq.mean_out : nullptr;
     // up to four workgroups per CU (the multi-GPU bench keeps CUs free through grid_blocks); never more than there are rows for
     int64_t blocks = e->grid_blocks > 0 ? e->grid_blocks : (int64_t)e->num_cus * 4;
     const int64_t need = (N + LOOKUP_THREADS - 1) / LOOKUP_THREADS;
@@ -86,7 +86,7 @@ int fx_launch_score_cnn_lookup(fx_engine* e, fx_model* const* models, int M, con
         default: return FX_EUNSUPPORTED;
     }
     FX_HIP(e, hipGetLastError());
-    if (fuse) e->fused_mean_done = true;
+    if (fuse) out.mean_done = true;
     e->counters.pool_table_launches += 1;
     e->counters.score_table_launches += 1;
     return FX_OK;

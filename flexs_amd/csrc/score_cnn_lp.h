@@ -393,7 +393,7 @@ __global__ void __launch_bounds__(256) k_score_cnn_lp(PairArgs p) {
 
 // Launches the LP form when it applies: FX_EUNSUPPORTED otherwise (the caller carries on with the SEG / whole-sequence forms).
 template <int A, int K, int HT>
-int launch_lp(fx_engine* e, PairArgs a, size_t lds_bytes) {
+int launch_lp(fx_engine* e, const FxRequest& rq, FxOutcome& out, PairArgs a, size_t lds_bytes) {
     constexpr int PBW = 8, K3 = A - 1;
     const int64_t U = (int64_t)a.M * a.TG;
     const int L1 = a.L - K + 1;
@@ -449,7 +449,7 @@ int launch_lp(fx_engine* e, PairArgs a, size_t lds_bytes) {
         if (e->done_seq >= 0x7FFFFFFFu) e->done_seq = 1;   // (a pre-launched instance reports (sequence << 1) | 1)
         a.lp_done = e->d_done; a.lp_done_seq = e->done_seq;
         e->done_armed = true;
-        if (e->lp_arm_next && e->lp_mail && e->d_lp_state) {
+        if (rq.arm_next && e->lp_mail && e->d_lp_state) {
             a.lp_mail = e->lp_mail;
             a.ascii = e->lp_mail->bytes;
             a.lp_word = ((unsigned long long)e->done_seq << 16) | (unsigned long long)a.N;
@@ -458,7 +458,7 @@ int launch_lp(fx_engine* e, PairArgs a, size_t lds_bytes) {
             a.lp_decide = e->d_lp_bar + 18 * 32;
         }
     }
-    e->lp_launches += 1;
+    out.lp_launches += 1;
     const int64_t G = U * nb;
     const bool arrives = !(a.lp_debug >= 1 && a.lp_debug <= 3);   // (profiling stages that leave before the barrier do not arrive at it)
     for (int gi = 0; gi < 16; ++gi) {

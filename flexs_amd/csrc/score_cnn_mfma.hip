@@ -3,7 +3,7 @@
 #include "score_cnn_kernel.h"
 
 int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                             int64_t N, float* d_out_NM, int Mtot, int m_off) {
+                             int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out) {
     if (N == 0) return FX_OK;
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
@@ -12,9 +12,9 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
         if (t.kind != FX_CNN || t.L != s.L || t.A != s.A || t.F != s.F || t.H != s.H || t.K != s.K)
             return FX_EUNSUPPORTED;                      // heterogeneous: caller scores them one by one
     }
-    if (int rc = fx_cnn_fused_supported(e, s, lay, M)) return rc;
-    if (!e->rows_req.on) {
-        const int rc = fx_launch_score_cnn_quad(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off);
+    if (int rc = fx_cnn_fused_supported(e, rq, s, lay, M)) return rc;
+    if (!rq.rows_on) {
+        const int rc = fx_launch_score_cnn_quad(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, rq, out);
         if (rc != FX_EUNSUPPORTED) return rc;
     }
 
@@ -24,7 +24,7 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
     a.wave_prio = (int)e->wave_prio;
     a.stage_fill = (int)e->stage_fill;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.N = N; a.M = M; a.Mtot = Mtot; a.m_off = m_off; a.L = s.L; a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
     a.off_first = (int)lay.off_first; a.off_c2 = (int)lay.off_c2; a.off_c3 = (int)lay.off_c3;
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
@@ -36,16 +36,16 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
     // mean-only call with the rows resident in device memory and every member in this launch: the last member to finish a tile averages
     // it (fx_fused_mean_tile) -- no mean kernel behind the launch.  (Rows that arrive while the kernel runs keep the mean kernel: a
     // starved launch is redone, and its tickets would be left half drawn.)
-    if (e->fuse_mean_batch_out && e->planar_stride && m_off == 0 && M == Mtot && M > 1 && M < 8 && !e->rows_req.on) {
+    if (e->fuse_mean_batch && rq.mean_out && rq.stride && m_off == 0 && M == Mtot && M > 1 && M < 8 && !rq.rows_on) {
         void* ws = nullptr;
         if (int rc = fx_zero_pool(e, (size_t)((N + 15) / 16) * sizeof(unsigned), &ws)) return rc;
-        a.fm_mean = e->fuse_mean_batch_out;
+        a.fm_mean = rq.mean_out;
         a.fm_cnt = (unsigned*)ws;
     }
 #endif
-    const CnnPick pk = fx_cnn_pick_fused(e, s, lay, N, M);
+    const CnnPick pk = fx_cnn_pick_fused(e, rq, s, lay, N, M);
     if (pk.pair_first && e->cnn_pair) {
-        const int rc = fx_launch_score_cnn_pair(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off);
+        const int rc = fx_launch_score_cnn_pair(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, rq, out);
         if (rc != FX_EUNSUPPORTED) return rc;
     }
     if (pk.rc) return pk.msg ? fx_fail(e, pk.rc, pk.msg) : pk.rc;
@@ -54,18 +54,18 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
         // in-kernel timeline and the fused mean of the A/B build belong to the conv forms
         bool fresh = true;
         for (int m = 0; m < M; ++m) fresh = fresh && models[m]->d_pooltab && models[m]->pooltab_version == models[m]->version;
-        CnnPoolDecision pool = fx_cnn_pool_decide(e, lay, pk, N, fresh);
+        CnnPoolDecision pool = fx_cnn_pool_decide(e, rq, lay, pk, N, fresh);
         if (a.trace) pool = CNN_POOL_NO;
 #if defined(FX_AB)
         if (a.fm_mean) pool = CNN_POOL_NO;
 #endif
         if (fx_cnn_score_decide(e, pool) == CNN_SCORE_LOOKUP) {
             // ... or nothing runs but a table read per row and member (score_cnn_lookup.hip)
-            const int rc = fx_launch_score_cnn_lookup(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, pool == CNN_POOL_BUILD);
+            const int rc = fx_launch_score_cnn_lookup(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, rq, out, pool == CNN_POOL_BUILD);
             if (rc != FX_EUNSUPPORTED) return rc;       // (no score table could be had: the head-only form)
         }
         if (pool != CNN_POOL_NO) {
-            const int rc = fx_launch_score_cnn_pooled(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, pool == CNN_POOL_BUILD);
+            const int rc = fx_launch_score_cnn_pooled(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, rq, out, pool == CNN_POOL_BUILD);
             if (rc != FX_EUNSUPPORTED) return rc;       // (no table could be had: the form picked above)
         }
     }
@@ -81,7 +81,7 @@ int fx_launch_score_cnn_mfma(fx_engine* e, fx_model* const* models, int M, const
         a.seg_pool = (unsigned*)ws;
         a.seg_cnt = (unsigned*)((char*)ws + pool_bytes);
     }
-    return fx_cnn_with_fused_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, a, pk.lds); });
+    return fx_cnn_with_fused_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, rq, out, a, pk.lds); });
 }
 
 #include "score_cnn_tables.h"   // fx_build_conv1_table, fx_build_conv2_prefix (why here: its first lines)

@@ -340,7 +340,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_cnn_pair(PairArgs p) {
 #include "score_cnn_lp.h"   // k_score_cnn_lp + launch_lp (the layer-parallel small-batch form)
 
 template <int A, int K, int HT, int WAVES>
-int launch_pair(fx_engine* e, PairArgs a, size_t lds_bytes) {
+int launch_pair(fx_engine* e, const FxRequest& rq, FxOutcome& out, PairArgs a, size_t lds_bytes) {
     auto whole = k_score_cnn_pair<A, K, HT, WAVES, false>;
     auto seg = k_score_cnn_pair<A, K, HT, WAVES, true>;
     static bool attr_set[64] = {};
@@ -351,7 +351,7 @@ int launch_pair(fx_engine* e, PairArgs a, size_t lds_bytes) {
     }
     const int64_t U = (int64_t)a.M * a.TG;
     const int L1 = a.L - K + 1;
-    if (e->cnn_pair_seg < 0 && !e->rows_req.on && U > e->num_cus && U <= 2 * (int64_t)e->num_cus && a.TG >= 2 && a.out) {
+    if (e->cnn_pair_seg < 0 && !rq.rows_on && U > e->num_cus && U <= 2 * (int64_t)e->num_cus && a.TG >= 2 && a.out) {
         // Between one and two units per CU (round 6) the whole-sequence form below is ONE serial walk per wave pair with half the pairs idle
         // (1.47 ms at 237 residues whatever the count); two launches of the segmented form, half the tiles each, are two walks of a third
         // of the length (3 x 2000 GFP sequences: 1466 -> 960 us)
@@ -359,8 +359,8 @@ int launch_pair(fx_engine* e, PairArgs a, size_t lds_bytes) {
         const int64_t t_half = (a.TG + 1) / 2;
         lo.TG = t_half; lo.N = a.N < t_half * 16 ? a.N : t_half * 16;
         hi.TG = a.TG - t_half; hi.N = a.N - t_half * 16; hi.ascii = a.ascii + t_half * 16 * a.L; hi.out = a.out + t_half * 16 * a.out_sn;
-        if (int rc = launch_pair<A, K, HT, WAVES>(e, lo, lds_bytes)) return rc;
-        return launch_pair<A, K, HT, WAVES>(e, hi, lds_bytes);
+        if (int rc = launch_pair<A, K, HT, WAVES>(e, rq, out, lo, lds_bytes)) return rc;
+        return launch_pair<A, K, HT, WAVES>(e, rq, out, hi, lds_bytes);
     }
     // Small batch (a CMA-ES / DyNA-PPO population, a single sequence): fewer units than half the CUs.  Cut every
     // tile into segments over SB workgroups so that the call's latency is ~L1/S + halo steps.  The halo (PL3 + PL2 +
@@ -376,7 +376,7 @@ int launch_pair(fx_engine* e, PairArgs a, size_t lds_bytes) {
         if constexpr (A == 20 && K == 5 && HT == 7 && WAVES == 8) {
             // layer-parallel form first (no halo recomputation): canonical protein CNN, units x position blocks <= CUs
             if (e->cnn_pair_seg < 0) {
-                const int rc_lp = launch_lp<A, K, HT>(e, a, lds_bytes);
+                const int rc_lp = launch_lp<A, K, HT>(e, rq, out, a, lds_bytes);
                 if (rc_lp != FX_EUNSUPPORTED) return rc_lp;
             }
         }
@@ -481,7 +481,7 @@ int fx_launch_cnn_pair_conv(fx_engine* e, fx_model* const* models, int M, const 
 }
 
 int fx_launch_score_cnn_pair(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                             float* d_out_NM, int Mtot, int m_off) {
+                             float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out) {
     if (N == 0) return FX_OK;
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
@@ -493,21 +493,21 @@ int fx_launch_score_cnn_pair(fx_engine* e, fx_model* const* models, int M, const
     PairArgs a{};
     a.ascii = d_ascii; a.lut = e->d_lut; a.out = d_out_NM; a.err = e->d_err;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.N = N; a.TG = (N + 15) / 16; a.M = M; a.Mtot = Mtot; a.m_off = m_off; a.L = s.L; a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
     a.off_c2 = (int)lay.off_c2; a.off_c3 = (int)lay.off_c3; a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p;
     a.conv_floats = (int)lay.conv_floats; a.lds_from = (int)lay.off_c2; a.lds_floats = (int)(lay.conv_floats - lay.off_c2); a.off_d1 = (int)lay.off_d1; a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db;
     a.lp_head_floats = (lay.off_d1 % 4 == 0) ? (int)(lay.total_floats - lay.off_d1) : 0;   // (0: no layer-parallel form)
-    if (s.K == 3) return launch_pair<20, 3, 7, WAVES>(e, a, lds);
-    if (s.K == 7) return launch_pair<20, 7, 7, WAVES>(e, a, lds);
+    if (s.K == 3) return launch_pair<20, 3, 7, WAVES>(e, rq, out, a, lds);
+    if (s.K == 7) return launch_pair<20, 7, 7, WAVES>(e, rq, out, a, lds);
     switch (lay.HT) {
-        case 1: return launch_pair<20, 5, 1, WAVES>(e, a, lds);
-        case 2: return launch_pair<20, 5, 2, WAVES>(e, a, lds);
-        case 4: return launch_pair<20, 5, 4, WAVES>(e, a, lds);
-        case 7: return launch_pair<20, 5, 7, WAVES>(e, a, lds);
-        case 8: return launch_pair<20, 5, 8, WAVES>(e, a, lds);
-        case 13: return launch_pair<20, 5, 13, WAVES>(e, a, lds);
-        case 16: return launch_pair<20, 5, 16, WAVES>(e, a, lds);
+        case 1: return launch_pair<20, 5, 1, WAVES>(e, rq, out, a, lds);
+        case 2: return launch_pair<20, 5, 2, WAVES>(e, rq, out, a, lds);
+        case 4: return launch_pair<20, 5, 4, WAVES>(e, rq, out, a, lds);
+        case 7: return launch_pair<20, 5, 7, WAVES>(e, rq, out, a, lds);
+        case 8: return launch_pair<20, 5, 8, WAVES>(e, rq, out, a, lds);
+        case 13: return launch_pair<20, 5, 13, WAVES>(e, rq, out, a, lds);
+        case 16: return launch_pair<20, 5, 16, WAVES>(e, rq, out, a, lds);
         default: return FX_EUNSUPPORTED;
     }
 }

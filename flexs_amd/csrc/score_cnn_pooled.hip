@@ -134,7 +134,8 @@ int build_pool_table(fx_engine* e, fx_model* m) {
     if (lds > (size_t)e->max_lds) return FX_EUNSUPPORTED;
     const int64_t blocks = e->grid_blocks;
     e->grid_blocks = 0;
-    const int rc = launch_g<CnnPoolTableBuild>(e, a, lds);
+    FxOutcome out;                                       // (a launch of the build's own, outside any dispatch: the default request)
+    const int rc = launch_g<CnnPoolTableBuild>(e, FxRequest{}, out, a, lds);
     e->grid_blocks = blocks;
     if (rc) return rc;
     m->pooltab_version = m->version;
@@ -143,10 +144,10 @@ int build_pool_table(fx_engine* e, fx_model* m) {
 }
 
 // Whether the head-only kernel serves this shape on this engine, and the LDS it asks for.
-bool pooled_supported(const fx_engine* e, const FxPackLayout& lay, int M, size_t* lds) {
+bool pooled_supported(const fx_engine* e, const FxRequest& rq, const FxPackLayout& lay, int M, size_t* lds) {
     const int64_t head_floats = lay.total_floats - lay.off_d1;
     *lds = (size_t)head_floats * 4 + 256 + 48;
-    return !(M > FX_MAX_M || lay.off_c1tab < 0 || lay.off_d1 % 4 || head_floats % 4 || *lds > (size_t)e->max_lds || e->rows_req.on);
+    return !(M > FX_MAX_M || lay.off_c1tab < 0 || lay.off_d1 % 4 || head_floats % 4 || *lds > (size_t)e->max_lds || rq.rows_on);
 }
 
 // Every member's pooled-feature table fresh: the stale ones are built when `build`.  FX_EUNSUPPORTED: one is stale and stays so.
@@ -205,25 +206,25 @@ int build_score_table(fx_engine* e, fx_model* m, size_t lds) {
 }  // namespace
 
 int fx_launch_score_cnn_pooled(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N, float* d_out_NM, int Mtot, int m_off,
-                               bool build) {
+                               const FxRequest& rq, FxOutcome&, bool build) {
     if (N == 0) return FX_OK;
     const FxPackLayout& lay = models[0]->layout;
     size_t lds = 0;
-    if (!pooled_supported(e, lay, M, &lds)) return FX_EUNSUPPORTED;
+    if (!pooled_supported(e, rq, lay, M, &lds)) return FX_EUNSUPPORTED;
     if (int rc = fresh_pool_tables(e, models, M, build)) return rc;
     PooledArgs a{};
     a.ascii = d_ascii; a.out = d_out_NM;
     for (int m = 0; m < M; ++m) { a.w[m] = models[m]->d_packed; a.tab[m] = models[m]->d_pooltab; }
     a.N = N; a.M = M; a.m_off = m_off;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     if (int rc = launch_pooled<false>(e, a, lay, lds, e->grid_blocks > 0 ? e->grid_blocks : e->num_cus)) return rc;
     e->counters.pool_table_launches += 1;
     return FX_OK;
 }
 
-int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, bool build_pool) {
+int fx_cnn_score_tables(fx_engine* e, fx_model* const* models, int M, const FxRequest& rq, bool build_pool) {
     size_t lds = 0;
-    if (!pooled_supported(e, models[0]->layout, M, &lds)) return FX_EUNSUPPORTED;
+    if (!pooled_supported(e, rq, models[0]->layout, M, &lds)) return FX_EUNSUPPORTED;
     if (int rc = fresh_pool_tables(e, models, M, build_pool)) return rc;
     for (int m = 0; m < M; ++m) {
         fx_model* mo = models[m];

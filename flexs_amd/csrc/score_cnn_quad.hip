@@ -419,7 +419,7 @@ int launch_quad(fx_engine* e, QuadArgs a, int64_t U, int max_rounds) {
 
 // FX_EUNSUPPORTED when the quad form does not apply (the caller carries on with the one-wave-per-tile kernels).
 int fx_launch_score_cnn_quad(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                             float* d_out_NM, int Mtot, int m_off) {
+                             float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out) {
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
     const int L1 = s.L - s.K + 1;
@@ -434,19 +434,19 @@ int fx_launch_score_cnn_quad(fx_engine* e, fx_model* const* models, int M, const
     if (int rc = fx_trace_buffer(e, &a.trace)) return rc;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
     a.N = N; a.TG = TG; a.M = M; a.m_off = m_off;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.L = s.L; a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
     a.rotate = (int)e->quad_rotate;
     a.dma = e->dma_fill && lay.off_d1 % 4 == 0 && lay.total_floats % 4 == 0;
 #if defined(FX_AB)
-    const bool fuse = e->fuse_mean_out && e->planar_stride && m_off == 0 && M == Mtot && M <= 16 && TG <= 4096;
+    const bool fuse = e->fuse_mean && rq.mean_out && rq.stride && m_off == 0 && M == Mtot && M <= 16 && TG <= 4096;
 #else
     const bool fuse = false;
 #endif
     if (fuse) {
         void* tk = nullptr;
         if (int rc = fx_zero_pool(e, sizeof(unsigned) * (size_t)TG, &tk)) return rc;
-        a.mean_out = e->fuse_mean_out;
+        a.mean_out = rq.mean_out;
         a.tickets = (unsigned*)tk;
     }
     const int rc_q = [&]() -> int {
@@ -467,7 +467,7 @@ int fx_launch_score_cnn_quad(fx_engine* e, fx_model* const* models, int M, const
     if (L1 < 4) return launch_quad<3, 8, 0>(e, a, U, 1);
     return launch_quad<1, 24, 0>(e, a, U, 2);
     }();
-    if (rc_q == FX_OK && fuse) e->fused_mean_done = true;
+    if (rc_q == FX_OK && fuse) out.mean_done = true;
     return rc_q;
 }
 

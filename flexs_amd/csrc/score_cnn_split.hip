@@ -193,7 +193,7 @@ int by_channel_tiles(int FT, Fn1 f1, Fn2 f2, Fn3 f3, Fn4 f4_) {
 }  // namespace
 
 int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                              float* d_out_NM, int Mtot, int m_off) {
+                              float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out) {
     if (N == 0) return FX_OK;
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
@@ -212,7 +212,7 @@ int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, cons
         HeadArgs hp{};
         hp.pool = (const f4*)pool; hp.out = d_out_NM; hp.N = N; hp.TG = TG; hp.M = M; hp.m_off = m_off;
         for (int m = 0; m < M; ++m) hp.w[m] = models[m]->d_packed;
-        hp.out_sn = e->planar_stride ? 1 : Mtot; hp.out_sm = e->planar_stride ? e->planar_stride : 1;
+        fx_out_strides(hp, rq, Mtot);
         hp.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
         hp.off_d1 = (int)lay.off_d1; hp.off_d2 = (int)lay.off_d2; hp.off_db = (int)lay.off_db;
         hp.head_floats = (int)(lay.total_floats - lay.off_d1);
@@ -222,15 +222,15 @@ int fx_launch_score_cnn_split(fx_engine* e, fx_model* const* models, int M, cons
     CnnArgs a{};
     a.ascii = d_ascii; a.lut = e->d_lut; a.out = d_out_NM; a.err = e->d_err;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.N = N; a.TG = TG; a.M = M; a.Mtot = Mtot; a.m_off = m_off; a.L = s.L; a.rlh = 4;
     a.off_first = (int)lay.off_first; a.off_c2 = (int)lay.off_c2; a.off_c3 = (int)lay.off_c3;
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
     a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
     a.pool_out = (f4*)pool;
-    const CnnPick pk = fx_cnn_pick_conv(e, s, lay, N, M);    // the conv-only form of the fused kernel (score_cnn_forms.h)
+    const CnnPick pk = fx_cnn_pick_conv(e, rq, s, lay, N, M);    // the conv-only form of the fused kernel (score_cnn_forms.h)
     if (pk.rc) return pk.rc;
-    if ((rc = fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, a, pk.lds); }))) return rc;
+    if ((rc = fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, rq, out, a, pk.lds); }))) return rc;
 
     HeadArgs h{};
     h.pool = (const f4*)pool; h.out = d_out_NM; h.N = N; h.TG = TG; h.M = M; h.m_off = m_off;
@@ -259,7 +259,9 @@ int fx_launch_cnn_conv_only(fx_engine* e, fx_model* model, const uint8_t* d_asci
     a.off_cb = (int)lay.off_cb; a.off_w1p = (int)lay.off_w1p; a.conv_floats = (int)lay.conv_floats; a.off_d1 = (int)lay.off_d1;
     a.off_d2 = (int)lay.off_d2; a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
     a.pool_out = (f4*)d_pool;
-    const CnnPick pk = fx_cnn_pick_conv(e, s, lay, N, 1);
+    const FxRequest rq;                                  // (a test hook, outside any dispatch: the default request)
+    FxOutcome out;
+    const CnnPick pk = fx_cnn_pick_conv(e, rq, s, lay, N, 1);
     if (pk.rc) return pk.rc;
-    return fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, a, pk.lds); });
+    return fx_cnn_with_conv_form(pk, [&](auto form) { return launch_g<decltype(form)>(e, rq, out, a, pk.lds); });
 }

@@ -587,7 +587,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_score_dense_mfma(DenseArgs p) {
 
 template <int KIND, int A, int HT, int NT, int WAVES, bool G1, bool W1G = false, bool DG = false, bool SLAB = false, bool BT = false,
           bool PAIR = false, bool PF = false>
-int launch_inst(fx_engine* e, const DenseArgs& a_in, size_t lds_bytes) {
+int launch_inst(fx_engine* e, const FxRequest& rq, FxOutcome& out, const DenseArgs& a_in, size_t lds_bytes) {
     auto kern = k_score_dense_mfma<KIND, A, HT, NT, WAVES, G1, W1G, DG, SLAB, BT, PAIR, PF>;
     if (SLAB) lds_bytes += (size_t)2 * FX_SLAB_KG * HT * 1024;  // two slabs of KG input tiles
     static bool attr_set[64] = {};
@@ -597,18 +597,18 @@ int launch_inst(fx_engine* e, const DenseArgs& a_in, size_t lds_bytes) {
         attr_set[e->device & 63] = true;
     }
     DenseArgs a = a_in;
-    if (e->rows_req.on) {
+    if (rq.rows_on) {
         // (a launched-first call: this kernel waits for its rows tile by tile -- the lockstep slab form does not)
         if (SLAB || NT != 1) return FX_EUNSUPPORTED;
-        if (e->rows_req.relay.flags) {
+        if (rq.relay.flags) {
             // the relay: the forms that copy a tile's bytes into LDS first, one launch for the whole ensemble
             if (!((PAIR || BT) && a.stage_stride > 0) || a.M < 2 || a.m_off != 0 || a.M != a.Mtot) return FX_EUNSUPPORTED;
         }
-        if (!fx_rows_plan(e)) return FX_EUNSUPPORTED;
-        a.ready = e->rows_req.r;
-        a.relay = e->rows_req.relay;
-        e->rows_req.relay_used = a.relay.flags != nullptr;
-        e->rows_req.used = true;
+        if (!(out.Q = fx_rows_plan(rq.min_share))) return FX_EUNSUPPORTED;
+        a.ready = rq.rows; a.ready.Q = out.Q;
+        a.relay = rq.relay;
+        out.relay_used = a.relay.flags != nullptr;
+        out.rows_used = true;
     }
     const int64_t U = (int64_t)a.M * a.TG;
     int64_t blocks = e->grid_blocks > 0 ? e->grid_blocks : e->num_cus;
@@ -630,14 +630,14 @@ int launch_inst(fx_engine* e, const DenseArgs& a_in, size_t lds_bytes) {
 namespace {
 
 // dense_prefetch: 1 = where it was measured to pay (a relay of at least four members), 2 = every launch that reads host rows (A/B), 0 = never
-static bool fx_dense_prefetch_pays(const fx_engine* e, int M) {
+static bool fx_dense_prefetch_pays(const fx_engine* e, const FxRequest& rq, int M) {
     if (e->dense_prefetch == 2) return true;
-    return e->dense_prefetch == 1 && e->rows_req.on && e->rows_req.relay.flags != nullptr && M >= 4;
+    return e->dense_prefetch == 1 && rq.rows_on && rq.relay.flags != nullptr && M >= 4;
 }
 
 // HT <= 7: 16 waves (128-register budget); HT = 8: 8 waves; HT = 13 / 16 (H <= 256): 8 waves and the HxH blocks stream from L2.
 template <int HT_>
-int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, DenseArgs& a) {
+int dispatch_dense(fx_engine* e, const FxRequest& rq, FxOutcome& out, const FxShape& s, const FxPackLayout& lay, DenseArgs& a) {
     constexpr int W = HT_ <= 7 ? 16 : 8;
     constexpr bool DGc = HT_ > 8;
     // Mid-size launches (a handful of tiles per SIMD): two waves per SIMD instead of four.  With four, a SIMD's 5-7
@@ -661,17 +661,17 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
             if constexpr (HT_ <= 8) {
                 // software-pipelined form: one 32-position table trip per block row of the H x H layer
                 const size_t pneed = (size_t)a.Lpad * 128 + (size_t)a.lds_floats * 4 + 256 + 32 + 8 * stride;
-                if (e->dense_pipe && !e->rows_req.on && a.Lpad / 32 + 2 + 1 <= HT_ && s.L <= 128 && pneed <= (size_t)e->max_lds) {
+                if (e->dense_pipe && !rq.rows_on && a.Lpad / 32 + 2 + 1 <= HT_ && s.L <= 128 && pneed <= (size_t)e->max_lds) {
                     a.stage_stride = (int)stride;
-                    if (s.L <= 64) return launch_pipe<FX_GE, HT_, 1>(e, a, pneed);
-                    return launch_pipe<FX_GE, HT_, 2>(e, a, pneed);
+                    if (s.L <= 64) return launch_pipe<FX_GE, HT_, 1>(e, rq, out, a, pneed);
+                    return launch_pipe<FX_GE, HT_, 2>(e, rq, out, a, pneed);
                 }
             }
 #endif
             if (e->stage_bytes && need + W * stride <= (size_t)e->max_lds) { a.stage_stride = (int)stride; need += W * stride; }
 #if defined(FX_AB)
             if constexpr (HT_ == 7) {
-                if (few_waves) return launch_inst<FX_GE, 4, HT_, 1, 8, false, false, false, false, true>(e, a, need);
+                if (few_waves) return launch_inst<FX_GE, 4, HT_, 1, 8, false, false, false, false, true>(e, rq, out, a, need);
             }
 #endif
             if constexpr (W == 16) {
@@ -690,10 +690,10 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
                 // (where it pays: a relay, whose few copying waves see the link's full latency -- 8 x GE L=90: 285 -> 234 us per
                 //  launch; without a relay every wave reads for itself and claiming a tile ahead costs more than it hides: MLP L=14
                 //  93 -> 101 us, 3 x GE with a relay 175 -> 183: profiles/r5_dense_prefetch.log)
-                if (e->ascii_host && fx_dense_prefetch_pays(e, a.M) && a.stage_stride > 0 && !a.coop && need + (size_t)W * stride <= (size_t)e->max_lds)
-                    return launch_inst<FX_GE, 4, HT_, 1, W, false, false, false, false, true, false, true>(e, a, need + (size_t)W * stride);
+                if (rq.host_rows && fx_dense_prefetch_pays(e, rq, a.M) && a.stage_stride > 0 && !a.coop && need + (size_t)W * stride <= (size_t)e->max_lds)
+                    return launch_inst<FX_GE, 4, HT_, 1, W, false, false, false, false, true, false, true>(e, rq, out, a, need + (size_t)W * stride);
             }
-            return launch_inst<FX_GE, 4, HT_, 1, W, false, false, false, false, true>(e, a, need);
+            return launch_inst<FX_GE, 4, HT_, 1, W, false, false, false, false, true>(e, rq, out, a, need);
         }
     }
     if (lds > (size_t)e->max_lds) {
@@ -710,9 +710,9 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
         // (rows that arrive while the kernel runs: the caller packs first instead -- nothing has been enqueued; rows in host memory: the
         //  position-major kernel reads two to four bytes per sequence and barrier, which is no pattern for PCIe -- the planner sends such
         //  calls down the copy path, fx_score.hip, and this is the net under it)
-        if (e->rows_req.on) return FX_EUNSUPPORTED;
+        if (rq.rows_on) return FX_EUNSUPPORTED;
     }
-    if (w1_global && fx_mlp_l1_pos_applies(e, s, lay) && !e->ascii_host && (int64_t)a.M * a.TG > (int64_t)e->num_cus * e->mlp_l1_pos_tiles) {
+    if (w1_global && fx_mlp_l1_pos_applies(e, s, lay) && !rq.host_rows && (int64_t)a.M * a.TG > (int64_t)e->num_cus * e->mlp_l1_pos_tiles) {
         // batch launch of an MLP whose first-layer rows do not fit LDS (protein alphabets): the first layer position-major into a scratch
         // (k_mlp_l1_pos: the rows cross L2 -> LDS once per 16-32 tiles instead of once per sequence), then this kernel from there
         // in slices of at most ~512 MB of scratch (a slice of 1e5 sequences x 200 hidden units is 83 MB; the rows of a batch are independent)
@@ -743,8 +743,8 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
             // ... and the H x H layers through LDS slabs where they do not fit (the image in LDS is empty: vectors and leftover tiles read L2)
             if (DGc && e->dense_slab && lds + (size_t)2 * FX_SLAB_KG * HT_ * 1024 <= (size_t)e->max_lds) {
                 a.slab_coop = e->dense_slab_coop > 0 ? (int)(e->dense_slab_coop < 7 ? e->dense_slab_coop : 7) : 0;
-                rc2 = launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc, DGc>(e, a, lds);
-            } else rc2 = launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc>(e, a, lds);
+                rc2 = launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc, DGc>(e, rq, out, a, lds);
+            } else rc2 = launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc>(e, rq, out, a, lds);
             if (rc2 != FX_OK) return rc2;
         }
         a.ascii = ascii_all; a.out = out_all; a.N = N_all; a.TG = TG_all; a.h1 = nullptr;
@@ -763,19 +763,19 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
                 a.lds_floats = 0;
                 a.off_w1pair = (int)lay.off_w1pair;
                 a.pair_floats = (int)lay.pair_floats;
-                return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, true, true, false, true>(e, a, (size_t)lay.pair_floats * 4 + 256 + 32);
+                return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, true, true, false, true>(e, rq, out, a, (size_t)lay.pair_floats * 4 + 256 + 32);
             }
-            if (s.kind == FX_MLP) return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, true, true>(e, a, lds);
-            return launch_inst<FX_GE, 4, HT_, 1, W, false, false, true, true>(e, a, lds);
+            if (s.kind == FX_MLP) return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, true, true>(e, rq, out, a, lds);
+            return launch_inst<FX_GE, 4, HT_, 1, W, false, false, true, true>(e, rq, out, a, lds);
         }
     }
     if (s.kind == FX_MLP) {
-        if (w1_global) return launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc>(e, a, lds);   // gather form: A is a runtime stride
+        if (w1_global) return launch_inst<FX_MLP, 4, HT_, 1, W, true, true, DGc>(e, rq, out, a, lds);   // gather form: A is a runtime stride
 #if defined(FX_AB)
         if (e->mlp_l1_mfma) {
             if constexpr (HT_ == 7) {
-                if (s.A == 4) return launch_inst<FX_MLP, 4, 7, 1, W, false, false, false>(e, a, lds);
-                if (s.A == 20) return launch_inst<FX_MLP, 20, 7, 1, W, false, false, false>(e, a, lds);
+                if (s.A == 4) return launch_inst<FX_MLP, 4, 7, 1, W, false, false, false>(e, rq, out, a, lds);
+                if (s.A == 20) return launch_inst<FX_MLP, 20, 7, 1, W, false, false, false>(e, rq, out, a, lds);
             }
             return FX_EUNSUPPORTED;
         }
@@ -793,37 +793,37 @@ int dispatch_dense(fx_engine* e, const FxShape& s, const FxPackLayout& lay, Dens
                     a.pair_floats = (int)lay.pair_floats;
 #if defined(FX_AB)
                     // software-pipelined form: one pair-row gather per block row of the two H x H layers
-                    if (e->dense_pipe && !e->rows_req.on && s.L / 2 + (s.L & 1) + 2 + 3 <= 2 * HT_ && s.L <= 32 && need + 8 * stride <= (size_t)e->max_lds) {
+                    if (e->dense_pipe && !rq.rows_on && s.L / 2 + (s.L & 1) + 2 + 3 <= 2 * HT_ && s.L <= 32 && need + 8 * stride <= (size_t)e->max_lds) {
                         a.stage_stride = (int)stride;
-                        return launch_pipe<FX_MLP, HT_, 1>(e, a, need + 8 * stride);
+                        return launch_pipe<FX_MLP, HT_, 1>(e, rq, out, a, need + 8 * stride);
                     }
 #endif
                     if (e->stage_bytes && need + W * stride <= (size_t)e->max_lds) { a.stage_stride = (int)stride; need += W * stride; }
 #if defined(FX_AB)
                     if constexpr (HT_ == 7) {
-                        if (few_waves) return launch_inst<FX_MLP, 4, HT_, 1, 8, true, false, false, false, false, true>(e, a, need);
+                        if (few_waves) return launch_inst<FX_MLP, 4, HT_, 1, 8, true, false, false, false, false, true>(e, rq, out, a, need);
                     }
 #endif
                     // shared last tiles: the groups' exchange buffers (2 x HT KiB each) lie over the pair rows
                     if (W == 16 && e->dense_coop)
                         a.coop = (size_t)lay.pair_floats * 4 >= (size_t)4 * HT_ * 1024 ? 2 : (size_t)lay.pair_floats * 4 >= (size_t)2 * HT_ * 1024 ? 1 : 0;
                     if constexpr (W == 16) {
-                        if (e->ascii_host && fx_dense_prefetch_pays(e, a.M) && a.stage_stride > 0 && need + (size_t)W * stride <= (size_t)e->max_lds)
-                            return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, false, false, false, true, true>(e, a, need + (size_t)W * stride);
+                        if (rq.host_rows && fx_dense_prefetch_pays(e, rq, a.M) && a.stage_stride > 0 && need + (size_t)W * stride <= (size_t)e->max_lds)
+                            return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, false, false, false, true, true>(e, rq, out, a, need + (size_t)W * stride);
                     }
-                    return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, false, false, false, true>(e, a, need);
+                    return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, false, false, false, true>(e, rq, out, a, need);
                 }
             }
         }
-        return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, DGc>(e, a, lds);
+        return launch_inst<FX_MLP, 4, HT_, 1, W, true, false, DGc>(e, rq, out, a, lds);
     }
-    return launch_inst<FX_GE, 4, HT_, 1, W, false, false, DGc>(e, a, lds);    // A is a runtime stride for GE
+    return launch_inst<FX_GE, 4, HT_, 1, W, false, false, DGc>(e, rq, out, a, lds);    // A is a runtime stride for GE
 }
 
 }  // namespace
 
 int fx_launch_score_dense_mfma(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                               float* d_out_NM, int Mtot, int m_off) {
+                               float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome& out) {
     if (N == 0) return FX_OK;
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
@@ -833,8 +833,8 @@ int fx_launch_score_dense_mfma(fx_engine* e, fx_model* const* models, int M, con
     }
     if ((s.kind != FX_MLP && s.kind != FX_GE) || M > FX_MAX_M) return FX_EUNSUPPORTED;
     if (s.A > 127) return FX_EUNSUPPORTED;                        // the gathers' bad-character test ORs the codes: needs code < 0x80
-    if (!e->rows_req.on) {                                        // (a launched-first host call is big: the persistent forms only)
-        const int rc = fx_launch_score_mlp_small(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off);
+    if (!rq.rows_on) {                                            // (a launched-first host call is big: the persistent forms only)
+        const int rc = fx_launch_score_mlp_small(e, models, M, d_ascii, N, d_out_NM, Mtot, m_off, rq, out);
         if (rc != FX_EUNSUPPORTED) return rc;
     }
     DenseArgs a{};
@@ -842,7 +842,7 @@ int fx_launch_score_dense_mfma(fx_engine* e, fx_model* const* models, int M, con
     if (int rc = fx_trace_buffer(e, &a.trace)) return rc;
     a.wave_prio = (int)e->wave_prio;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.N = N; a.M = M; a.Mtot = Mtot; a.m_off = m_off; a.L = s.L; a.A = s.A; a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
     a.SG1 = lay.SG1; a.off_first = (int)lay.off_first; a.off_w1p = (int)lay.off_w1p; a.off_d2 = (int)lay.off_d2; a.off_d3 = (int)lay.off_d3;
     a.off_db = (int)lay.off_db; a.total_floats = (int)lay.total_floats;
@@ -875,13 +875,13 @@ int fx_launch_score_dense_mfma(fx_engine* e, fx_model* const* models, int M, con
         }
     }
     switch (lay.HT) {
-        case 1: return dispatch_dense<1>(e, s, lay, a);
-        case 2: return dispatch_dense<2>(e, s, lay, a);
-        case 4: return dispatch_dense<4>(e, s, lay, a);
-        case 7: return dispatch_dense<7>(e, s, lay, a);
-        case 8: return dispatch_dense<8>(e, s, lay, a);
-        case 13: return dispatch_dense<13>(e, s, lay, a);
-        case 16: return dispatch_dense<16>(e, s, lay, a);
+        case 1: return dispatch_dense<1>(e, rq, out, s, lay, a);
+        case 2: return dispatch_dense<2>(e, rq, out, s, lay, a);
+        case 4: return dispatch_dense<4>(e, rq, out, s, lay, a);
+        case 7: return dispatch_dense<7>(e, rq, out, s, lay, a);
+        case 8: return dispatch_dense<8>(e, rq, out, s, lay, a);
+        case 13: return dispatch_dense<13>(e, rq, out, s, lay, a);
+        case 16: return dispatch_dense<16>(e, rq, out, s, lay, a);
         default: return FX_EUNSUPPORTED;
     }
 }

@@ -388,8 +388,8 @@ __global__ void __launch_bounds__(512) k_score_dense_pipe(DenseArgs p) {
 }
 
 template <int KIND, int HT, int NLD, int VAR>
-int launch_pipe_var(fx_engine* e, const DenseArgs& a, size_t lds_bytes) {
-    if (e->rows_req.on) return FX_EUNSUPPORTED;             // (this form asks for the next tile's bytes a tile ahead: not for rows that arrive during the run)
+int launch_pipe_var(fx_engine* e, const FxRequest& rq, const DenseArgs& a, size_t lds_bytes) {
+    if (rq.rows_on) return FX_EUNSUPPORTED;             // (this form asks for the next tile's bytes a tile ahead: not for rows that arrive during the run)
     auto kern = k_score_dense_pipe<KIND, HT, NLD, VAR>;
     static bool attr_set[64] = {};
     if (!attr_set[e->device & 63]) {
@@ -406,11 +406,11 @@ int launch_pipe_var(fx_engine* e, const DenseArgs& a, size_t lds_bytes) {
 }
 
 template <int KIND, int HT, int NLD>
-int launch_pipe(fx_engine* e, const DenseArgs& a, size_t lds_bytes) {
+int launch_pipe(fx_engine* e, const FxRequest& rq, FxOutcome&, const DenseArgs& a, size_t lds_bytes) {
     // dense_pipe: 1 = loads placed by the compiler, 2 = A operands double-buffered by hand (H <= 112: registers)
     if constexpr (HT <= 7) {
-        if (e->dense_pipe == 2) return launch_pipe_var<KIND, HT, NLD, 1>(e, a, lds_bytes);
+        if (e->dense_pipe == 2) return launch_pipe_var<KIND, HT, NLD, 1>(e, rq, a, lds_bytes);
     }
-    return launch_pipe_var<KIND, HT, NLD, 0>(e, a, lds_bytes);
+    return launch_pipe_var<KIND, HT, NLD, 0>(e, rq, a, lds_bytes);
 }
 

@@ -169,7 +169,7 @@ int launch_small_server(fx_engine* e, const SmallArgs& a, int M, hipStream_t str
 
 // FX_EUNSUPPORTED when the small-launch form does not apply (the caller carries on with the persistent kernel).
 int fx_launch_score_mlp_small(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii, int64_t N,
-                              float* d_out_NM, int Mtot, int m_off) {
+                              float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome&) {
     const FxShape& s = models[0]->shape;
     const FxPackLayout& lay = models[0]->layout;
     if (!e->dense_small || (s.kind != FX_MLP && s.kind != FX_GE) || M > FX_MAX_M || s.A > 127) return FX_EUNSUPPORTED;
@@ -181,7 +181,7 @@ int fx_launch_score_mlp_small(fx_engine* e, fx_model* const* models, int M, cons
     int64_t per_cu = (lay.HT > 8 || (s.kind == FX_MLP && (int64_t)s.L * s.A >= 160)) ? 4 : 1;
     // (an MLP whose first-layer rows do not fit LDS -- protein alphabets -- has the position-major first layer from 2 tiles per CU on, round 6:
     //  16 384 sequences of L = 90, H = 200 take this form 105 us, 30 000 take that one 106, profiles/r6_protein_mlp_wide.log)
-    if (fx_mlp_l1_pos_applies(e, s, lay) && !e->rows_req.on && !e->ascii_host) per_cu = e->mlp_l1_pos_tiles < per_cu ? e->mlp_l1_pos_tiles : per_cu;
+    if (fx_mlp_l1_pos_applies(e, s, lay) && !rq.rows_on && !rq.host_rows) per_cu = e->mlp_l1_pos_tiles < per_cu ? e->mlp_l1_pos_tiles : per_cu;
     if (e->dense_small < 2 && U > per_cu * e->num_cus) return FX_EUNSUPPORTED;
     const int form = s.kind == FX_MLP ? fx_mlp_first_layer_form(e, s, lay) : 0;
     if (form > 1) return FX_EUNSUPPORTED;
@@ -189,7 +189,7 @@ int fx_launch_score_mlp_small(fx_engine* e, fx_model* const* models, int M, cons
     a.ascii = d_ascii; a.lut = e->d_lut; a.out = d_out_NM; a.err = e->d_err;
     for (int m = 0; m < M; ++m) a.w[m] = models[m]->d_packed;
     a.N = N; a.TG = TG; a.M = M; a.m_off = m_off;
-    a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+    fx_out_strides(a, rq, Mtot);
     a.L = s.L; a.A = s.A; a.rlh = (lay.HTR == lay.HT) ? lay.RLH : 4;
     a.pair = form;
     a.off_w1p = (int)lay.off_w1p; a.off_w1pair = (int)lay.off_w1pair; a.off_d2 = (int)lay.off_d2; a.off_d3 = (int)lay.off_d3;

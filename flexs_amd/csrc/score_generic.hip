@@ -194,7 +194,7 @@ __global__ void k_score_generic_ge(GenericArgs a) {
 }  // namespace
 
 int fx_launch_score_generic(fx_engine* e, fx_model* const* models, int M, const uint8_t* d_ascii,
-                            int64_t N, float* d_out_NM, int Mtot, int m_off) {
+                            int64_t N, float* d_out_NM, int Mtot, int m_off, const FxRequest& rq, FxOutcome&) {
     if (N == 0) return FX_OK;
     for (int m = 0; m < M; ++m) {
         const FxShape& s = models[m]->shape;
@@ -221,7 +221,7 @@ int fx_launch_score_generic(fx_engine* e, fx_model* const* models, int M, const 
             a.ascii = d_ascii; a.lut = e->d_lut; a.blob = models[m]->d_blob; a.ws = (float*)ws;
             a.out = d_out_NM; a.err = e->d_err; a.N = N; a.n0 = n0; a.T = (int)T;
             a.L = s.L; a.A = s.A; a.F = s.F; a.H = s.H; a.K = s.K; a.Mtot = Mtot; a.m = m_off + m;
-            a.out_sn = e->planar_stride ? 1 : Mtot; a.out_sm = e->planar_stride ? e->planar_stride : 1;
+            fx_out_strides(a, rq, Mtot);
             a.rows1 = (int)rows1;
             dim3 grid((unsigned)((T + 255) / 256)), block(256);
             if (s.kind == FX_CNN) {
