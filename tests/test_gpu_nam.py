@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("L,nsym,C,Q", [(8, 4, 300, 200), (14, 4, 2500, 150), (66, 20, 700, 60), (90, 20, 1500, 40), (300, 20, 300, 12),
                                         (513, 20, 200, 8), (735, 20, 150, 6), (769, 20, 1100, 5), (1000, 4, 300, 7), (1600, 20, 40, 3),
                                         (238, 20, 300, 20), (64, 4, 200, 50), (65, 4, 200, 50), (1, 4, 10, 10),
-                                        # small caches, several queries per block (k_min_dist_small: C <= 128, L <= 32, Q >= 64)
+                                        # small caches (C <= 128, L <= 32, Q >= 64): k_min_dist<1, uint32_t>, one pass per block with the rows staged through LDS below 512 queries, four passes from global memory from 512 on
                                         (14, 4, 100, 2000), (8, 4, 17, 300), (32, 20, 128, 100), (14, 4, 1, 64), (31, 4, 127, 65), (5, 4, 16, 513)])
 def test_min_dist_vs_oracle(eng, L, nsym, C, Q):
     rng = np.random.default_rng(L * 7 + C)
@@ -70,7 +70,7 @@ def _ragged_strings(rng, n, lo, hi, alpha, base=None):
 
 @pytest.mark.parametrize("lo,hi,alpha,C,Q", [(0, 12, "TGCA", 400, 120), (50, 80, s_utils.AAS, 300, 40),
                                              (120, 200, s_utils.AAS, 150, 20), (1, 256, "UGCA", 60, 12),
-                                             (0, 12, "TGCA", 90, 130), (3, 30, s_utils.AAS, 120, 70)])      # small caches: k_min_dist_small over NUL-padded rows
+                                             (0, 12, "TGCA", 90, 130), (3, 30, s_utils.AAS, 120, 70)])      # small caches, NUL-padded rows of 12 / 19 and 30 / 37 bytes: k_min_dist<1, uint32_t> staged through LDS (37: the 64-bit word)
 def test_min_dist_ragged_lengths(eng, lo, hi, alpha, C, Q):
     """`editdistance.eval` takes two strings of any lengths (noisy_abstract_model.py:51): NUL-padded rows."""
     rng = np.random.default_rng(lo * 31 + hi)

@@ -10,6 +10,7 @@ import pytest
 from hypothesis import given, settings
 from hypothesis import strategies as st
 
+import distance_cases as dc
 import mfma_sim
 from flexs_amd import _native
 from oracle import c_oracle, ref_np
@@ -154,6 +155,70 @@ def test_myers_boundaries():
         assert _native.debug_myers(a, a[1:] + a[:1]) == c_oracle.levenshtein(a, a[1:] + a[:1])
     # beyond 768 symbols (12 words) the device runs the recurrence in strips of 768 pattern rows; so does the hook
     assert _native.debug_myers(b"x" * 769, b"x") == 768
+
+
+def test_distance_length_table_names_what_the_launchers_pick():
+    """tests/distance_cases.py LENGTH_FORMS against the launchers' rule restated (mindist.hip): every instantiation, the 32-bit
+    form, both sides of the staging bound and of the strip form are in the table."""
+    for L, form, staged in dc.LENGTH_FORMS:
+        assert dc.launcher_form(L) == (form, staged), L
+        assert dc.launcher_form(L) != dc.launcher_form(L + 1 if L % 2 == 0 else L - 1), L     # the table's pairs straddle a boundary
+    forms = {form for _, form, _ in dc.LENGTH_FORMS}
+    assert forms == {"W=1 uint32_t", "strips=2", "strips=3"} | {"W=%d" % w for w in (1, 2, 3, 4, 6, 8, 12)}
+    assert [L for L in dc.LENGTHS if L % 64 == 0 and L > 32] == [64, 128, 192, 256, 384, 512, 768, 1536]      # full last words
+
+
+@pytest.mark.parametrize("L", dc.LENGTHS + (14,))
+def test_myers_content_families_at_every_boundary(L):
+    """Host twin of tests/test_gpu_distances.py: the very inputs the device sees (distance_cases.build_case: unrelated rows, one
+    letter repeated, shifted copies, edits at bit 63 / bit 0 of every word, ragged and empty rows) through csrc/myers.h on the
+    host against the DP -- and the properties the families are built for, read off the DP."""
+    case = dc.reference(L)
+    lev, ham = case.dist
+    for i, q in enumerate(case.queries):
+        for j, k in enumerate(case.keys):
+            assert _native.debug_myers(q, k) == lev[i, j], (L, i, j)
+    parent = case.queries[0]
+    at = {k: j for j, k in enumerate(case.keys)}
+    assert lev[1, at[b"C" * L]] == L and ham[1, at[b"C" * L]] == L                         # family 2: every cell on the diagonal costs
+    assert lev[1, at[b"A" * (L // 2)]] == L - L // 2 and lev[1, at[b"A"]] == L - 1          # family 3, and the key of length 1
+    assert [lev[0, at[parent[s:] + parent[:s]]] for s in (1, 2, 3)] == [2, 4, 6]          # family 4
+    assert all(ham[0, at[parent[s:] + parent[:s]]] > L // 2 for s in (1, 2, 3))
+    assert all((lev[0] == d).any() and (ham[0] == d).any() for d in (0, 1, 2, 3, 4, 5))   # family 5: radius and radius + 1
+    assert lev[0].max() > L * 0.6                                                          # family 1: unrelated rows
+    wb = dc.word_boundary_length(L)
+    assert len(case.queries[2]) == wb and (L <= 64 or wb % 64 == 0) and L - 64 <= wb < L   # family 6
+    assert case.queries[3] == b"" and [lev[3, j] for j in range(len(case.keys))] == [len(k) for k in case.keys]
+    assert [lev[i, at[b""]] for i in range(len(case.queries))] == [len(q) for q in case.queries]
+    if L in dc.LENGTHS and L <= 769:                                                       # one edit at every word boundary
+        for p in dc.boundary_positions(L):
+            assert parent[:p] + parent[p + 1:] in at and any(len(k) == L and ham[0, j] == 1 and k[p] != parent[p] for k, j in at.items())
+
+
+@pytest.mark.parametrize("L", dc.REGISTER_LENGTHS + (14,))
+def test_bounded_band_content_families_up_to_768(L):
+    """csrc/myers.h fx_bounded_distance (k_distances_bounded) on the same inputs: min(d, K + 1) for K = 1 .. 3, both ways round,
+    Levenshtein and Hamming, at every length the device test runs the band at."""
+    case = dc.reference(L)
+    lev, ham = case.dist
+    for i, q in enumerate(case.queries):
+        for j, k in enumerate(case.keys):
+            for K in (1, 2, 3):
+                assert _native.debug_bounded_distance(q, k, K) == min(lev[i, j], K + 1), (L, i, j, K)
+                assert _native.debug_bounded_distance(k, q, K) == min(lev[i, j], K + 1), (L, j, i, K)
+                assert _native.debug_bounded_distance(q, k, K, hamming=True) == min(ham[i, j], K + 1), (L, i, j, K)
+
+
+@pytest.mark.parametrize("L", (32, 33, 64, 65))
+def test_selection_rule_case_is_what_it_says(L):
+    """distance_cases.selection_case: the hand-placed answers are what `ref_np.min_distance` gives over the DP, and csrc/myers.h
+    on the host gives the DP's distances for the placed keys."""
+    queries, keys, expected, what = dc.selection_case(L)
+    lev, ham = dc.dp_matrices(queries, keys, L)
+    assert [dc.select(r) for r in lev] == expected and [dc.select(r) for r in ham] == expected
+    for i, q in enumerate(queries):
+        for j in (3, 5, 255, 256, 300, 700, 1023, 1024, 1200, 1500, 1501):
+            assert _native.debug_myers(q, keys[j]) == lev[i, j]
 
 
 def test_myers_in_strips_for_patterns_of_any_length():
